@@ -74,6 +74,11 @@ def parse():
                          "training step + one denoising step, analytic FLOPs from the architecture, dominant kernel and its roofline fraction")
     ap.add_argument("--conv-math", choices=("bf16x3", "f32"), default=None,
                     help="arithmetic of the eligible 3x3 convolutions (default: the library default, bf16x3 split products)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float32, rank 0): train_loss = the loss of the last "
+                         "timed step, train_params = the parameters after it, sample_images = the images of the timed DDPM sampling leg; an array "
+                         "above its element budget is a fixed seeded sample of its flattened elements (under 64 MB in all).  Same arguments, "
+                         "same inputs: two builds can be compared file for file (e.g. DIR = bench_outputs/<build>)")
     return ap.parse_args()
 
 
@@ -224,6 +229,27 @@ def log(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_PARAMS_ELEMS = 1 << 23          # --dump-outputs element budgets (float32): 32 MiB of parameters + 16 MiB of sampled images < 64 MB
+DUMP_IMAGES_ELEMS = 1 << 22
+
+
+def dump_array(t: torch.Tensor, max_elems: int, seed: int):
+    """Host float32 copy of `t`; above `max_elems` elements, the flattened elements at a fixed seeded set of positions instead."""
+    t = t.detach()
+    if t.numel() > max_elems:
+        idx = torch.randint(0, t.numel(), (max_elems,), generator=torch.Generator().manual_seed(seed))
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.to("cpu", torch.float32).numpy()
+
+
+def write_dumps(path: str, arrays: dict):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    log(f"outputs written to {path}: " + ", ".join(f"{n} {tuple(a.shape)}" for n, a in arrays.items()))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` (N > 1, no torchrun around it): start N fresh rank processes -- one per GPU -- BEFORE this process makes any
     GPU call (it never does: it only waits), relay their output (rank 0 prints the one JSON line on the inherited stdout) and exit with the
@@ -309,6 +335,9 @@ def bench_secondary_config(args):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt)
     ips = world * B * args.steps / dt
+    dumps = {}
+    if args.dump_outputs and rank == 0:
+        dumps = {"train_loss": dump_array(loss.reshape(1), 1, 0), "train_params": dump_array(net.flat_param, DUMP_PARAMS_ELEMS, 1)}
     log(f"{args.config}: {ips:.2f} img/s ({1e3 * dt / args.steps:.2f} ms/step at per-GPU batch {B}), loss {float(loss):.4f}")
     # one no-grad denoising forward (graph replay as the samplers run it)
     from villandiffusion_amd.pipelines import sampler_forward
@@ -380,6 +409,8 @@ def bench_secondary_config(args):
             if path:
                 with open(path, "w") as f:
                     json.dump(dict(out, train_step_kernels=kernels), f)
+        if args.dump_outputs:
+            write_dumps(args.dump_outputs, dumps)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -492,6 +523,7 @@ def main():
     exact = None
     f16 = None
     ddp_path = None
+    dumps = {}                                           # --dump-outputs: host copies taken right after each timed region
     if do_train:
         for i in range(args.warmup):
             one_step(i)
@@ -512,6 +544,9 @@ def main():
         dt = float(tt)
         train_ips = world * B * args.steps / dt
         final_loss = float(loss)
+        if args.dump_outputs and rank == 0:
+            dumps["train_loss"] = dump_array(loss.reshape(1), 1, 0)
+            dumps["train_params"] = dump_array(net.flat_param, DUMP_PARAMS_ELEMS, 1)
         log(f"train: {train_ips:.1f} img/s ({1e3 * dt / args.steps:.2f} ms/step), loss {final_loss:.4f}")
         # host side of one step: time until the last launch of a step has been SUBMITTED (queue drained first) vs until it has run
         sub = []
@@ -629,6 +664,7 @@ def main():
         init = torch.empty((n_img, 3, 32, 32), device=dev)
         ops.randn(init, 7 + rank, 0)
         pp = torch.empty((n_img, 32, 32, 3), device=dev)
+        sampled = {}
 
         def sample_all(steps):
             chunks = torch.split(init, B)
@@ -649,7 +685,7 @@ def main():
             barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            sample_all(args.sample_steps)
+            sampled["images"] = sample_all(args.sample_steps)
             torch.cuda.synchronize()
             barrier()
             ts = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
@@ -659,6 +695,8 @@ def main():
 
         sample_s = timed_sampling()
         sample_ips = world * n_img / sample_s
+        if args.dump_outputs and rank == 0:
+            dumps["sample_images"] = dump_array(sampled["images"], DUMP_IMAGES_ELEMS, 2)
         assert bool(torch.isfinite(pp).all())
         log(f"sample: {sample_ips:.4f} img/s ({sample_s:.2f} s for {n_img} images x {args.sample_steps} steps; hip graph = {net.sampler_graph})")
         if net.sampler_graph and args.eager_sample:      # the same loop launched eagerly (what the graph replay replaces), reported beside it
@@ -881,6 +919,8 @@ def main():
         for tag, rows in (("train", kernels), ("sampler", sample_kernels)):
             for k in (rows or [])[:12]:
                 log(f"{tag:7s} {k['ms']:8.3f} ms {k['launches']:4d}x {k['avg_us']:8.1f} us  {k['bound']:4s} frac {k['frac']:.3f}  {k['kernel']}")
+        if args.dump_outputs:
+            write_dumps(args.dump_outputs, dumps)
         line = json.dumps(out)
         assert len(line) < 4096, len(line)
         print(line, flush=True)

@@ -255,3 +255,37 @@ def test_round5_lines_carry_ddp_path_and_counted_traffic():
     with open(os.path.join(P, "r05_pmc_mfma.json")) as f:
         m = json.load(f)["kernels"]
     assert m["wgrad_ps_group_kernel<32, 0>"]["MfmaUtil"] > 0.6 and m["wgrad_ps_group_kernel<16, 0>"]["MfmaUtil"] > 0.6
+
+
+# ---- --dump-outputs: what the timed steps computed, as .npy files, so that two builds can be compared output for output ----
+def test_dump_array_keeps_small_outputs_whole_and_samples_large_ones_at_fixed_positions():
+    import torch
+    import bench
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    a = bench.dump_array(small, 100, 0)
+    assert a.dtype.name == "float32" and a.shape == (3, 4) and (a == small.numpy()).all()
+    big = torch.arange(1000, dtype=torch.float32) * 0.5
+    s1, s2 = bench.dump_array(big, 64, 1), bench.dump_array(big.clone(), 64, 1)
+    assert s1.shape == (64,) and (s1 == s2).all()                          # same seed, same positions
+    assert ((s1 * 2) == (s1 * 2).round()).all() and s1.min() >= 0 and s1.max() <= 499.5   # every sampled value is an element of the input
+    assert not (bench.dump_array(big, 64, 2) == s1).all()
+    assert (bench.DUMP_PARAMS_ELEMS + bench.DUMP_IMAGES_ELEMS + 1) * 4 < 64e6
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_what_the_timed_steps_computed(tmp_path):
+    import numpy as np
+    out = tmp_path / "out"
+    r = _run_bench(["--steps", "3", "--warmup", "1", "--sample-images", "128", "--sample-steps", "20", "--no-cpu", "--no-exact", "--no-f16",
+                    "--no-secondary", "--no-roofline", "--no-ddp-path", "--dump-outputs", str(out)],
+                   {"VD_BENCH_DETAIL": str(tmp_path / "detail.json")}, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 128 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+    assert sorted(os.listdir(out)) == ["sample_images.npy", "train_loss.npy", "train_params.npy"]
+    loss, par, img = (np.load(out / f"{n}.npy") for n in ("train_loss", "train_params", "sample_images"))
+    assert loss.dtype == par.dtype == img.dtype == np.float32
+    assert loss.shape == (1,) and abs(float(loss[0]) - d["final_loss"]) <= 1e-5
+    assert par.shape == (1 << 23,) and img.shape == (128, 3, 32, 32)          # 35.7 M parameters: a fixed sample; the images whole
+    assert np.isfinite(par).all() and np.isfinite(img).all()
+    assert sum(os.path.getsize(out / n) for n in os.listdir(out)) < 64e6
