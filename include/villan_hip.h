@@ -106,6 +106,11 @@ typedef struct vd_gemm_desc {
     int32_t math;            /* 2: a_packed holds f16 operands (vd_conv3_pack_weights_f16_multi): ONE f16 MFMA per product term, f32 accumulation
                                 (~2e-4 relative per contraction) -- only problems the persistent 16x16x32 kernels take (vd_gemm_tile() 18 / 19),
                                 else VD_EINVAL.
+                                3: opt-in bf16 mixed precision: a_packed is the split-precision operand (vd_conv3_pack_weights), and ONE bf16 MFMA
+                                per product term multiplies its hi plane with the hi part of B (f32 B rounded to nearest even, a pre-split B's hi
+                                units, or the folded GroupNorm loader's bf16(silu(gn(x)))), f32 accumulation: the exact sum of bf16-rounded
+                                operands up to summation order.  Only problems of vd_gemm_tile() 18 / 19 / 20 (3x3 forward, flipped-tap input
+                                gradient, Upsample2D, gn_ss / act_out / gn_part / b_presplit as for math 0; 1x1 products); else VD_EINVAL.
                                 0: exact f32 MFMA (or a_packed).  1: split-precision product of two ACTIVATION matrices (attention
                                 scores / values and their gradients): per-batch A (a_bstride != 0), VD_B_PLAIN or VD_B_KCONTIG,
                                 NP % 128 == 0, K % 16 == 0, K >= 32, M >= 64, 16-byte aligned operands and strides; both operands
@@ -168,7 +173,10 @@ typedef struct vd_wgrad_desc {
     int32_t math;             /* 0: exact f32 MFMA.  1: split-precision bf16 MFMA (hi*hi + hi*lo + lo*hi, f32 accumulation,
                                  ~1e-5 relative): VD_B_CONV3 / VD_B_CONV3_UP with 8x8 / 16x16 / 32x32 outputs, either of them on images whose
                                  width is a multiple of 32 from 64 up, VD_B_CONV3 at 4x4, or VD_B_PLAIN (1x1) with
-                                 NP % 8 == 0; M >= 64, C >= 64; otherwise VD_EINVAL */
+                                 NP % 8 == 0; M >= 64, C >= 64; otherwise VD_EINVAL.
+                                 3: opt-in bf16 mixed precision, GROUPED launches only: one bf16 MFMA (hi(dY) * hi(X)) per product term, f32
+                                 accumulation, for the math = 1 problems whose class runs on the pre-split, 16x16x32 or wide 1x1 kernel
+                                 (vd_conv_wgrad_group_class() > 10000: a class of its own, never mixed with math = 1 jobs); vd_conv_wgrad: VD_EINVAL */
     int32_t presplit;         /* ABI 11, math == 1 only.  Bit 0: X, bit 1: dY is a PRE-SPLIT image (vd_presplit_* below) instead of f32 NCHW.
                                  3 (both): the kernel fetches both operands by LDS-DMA and reads them through ds_read_b64_tr_b16 -- no
                                  conversion, no staging registers (VD_B_CONV3 / VD_B_CONV3_UP at 8x8 / 16x16 / 32x32 outputs, M % 8 == C % 8 == 0,
@@ -207,7 +215,7 @@ int vd_groupnorm_bwd_presplit(const float* dy, const float* x, const float* mean
                               int B, int C, int HW, int G, int apply_silu, int64_t dy_bstride, int64_t x_bstride, int64_t extra_bstride,
                               int64_t extra2_bstride, int64_t dx_bstride, int64_t ps_bstride, int64_t rowsum_ld, void* stream);
 
-/* GROUPED weight gradients: several split-precision (math = 1) weight gradients of one kernel class in ONE launch pair (compute +
+/* GROUPED weight gradients: several split-precision (math = 1) or one-product (math = 3) weight gradients of one kernel class in ONE launch pair (compute +
  * fixed-order slab reduction).  A weight gradient has a small output and a huge reduction length (K = batch * pixels), so a launch
  * that must fill 256 CUs alone splits K over ~32 workgroups per tile and moves 32 partial copies of dW through memory; sharing the
  * grid between the convolutions of a whole gradient bucket keeps the chip full with ~3 splits per tile.  (The reference's autograd
@@ -219,7 +227,8 @@ int vd_groupnorm_bwd_presplit(const float* dy, const float* x, const float* mean
  *   launch : the two launches.  Deterministic (fixed reduction order); results agree with vd_conv_wgrad to summation order. */
 int vd_conv_wgrad_group_class(const vd_wgrad_desc* desc);
 int64_t vd_conv_wgrad_group_job_bytes(void);
-/* Kernel family a class runs on: 9 = all nine taps per workgroup (plain 3x3 at 16x16 / 32x32), 32 = opt-in 16x16x32 one-tap-row kernel, 0 = default. */
+/* Kernel family a class runs on: 9 = all nine taps per workgroup (plain 3x3 at 16x16 / 32x32), 32 = opt-in 16x16x32 one-tap-row kernel, 0 = default.
+ * A math = 3 class (10000 + the math = 1 class) runs on the same family as its math = 1 class, one product per term. */
 int vd_conv_wgrad_group_variant(int cls);
 int vd_conv_wgrad_group_plan(const vd_wgrad_desc* descs, int n, void* table_out, int64_t* ws_floats, int* blocks, int* rblocks);
 int vd_conv_wgrad_group_rebase(void* dev_table, int n, float* ws, void* stream);

@@ -61,9 +61,12 @@ struct k32p_args {
 // PS (round 5, vd_gemm_desc.b_presplit): the input is a PRE-SPLIT image (vd_presplit.hip: unit (octet, pixel, part) = the 8 channels of a pixel as bf16
 // hi / lo, 16 bytes, at ((octet * HW + pixel) * 2 + part) * 16) written by its producer -- a patch item is then two 16-byte loads that go to LDS as they
 // are: no conversion (24 VALU instructions per item), 2 instead of 8 loads per item.  Same values, same LDS image, same MFMA order: same bits.
-template <int TW, int MODE, bool DMA, bool PIPE, bool F16, bool PS = false>   // MODE 0: CONV3, 1: CONV3_T (flipped taps), 2: CONV3_UP, 3: CONV3 of silu(GroupNorm(x))
+// ONE (vd_gemm_desc.math = 3, opt-in bf16 mixed precision): the same operands, stages and LDS images; the fragment loop reads the hi planes only and
+// issues hi*hi -- one bf16 MFMA per product term.  The loaders still move (hi, lo) units (the lo planes are simply not read).
+template <int TW, int MODE, bool DMA, bool PIPE, bool F16, bool PS = false, bool ONE = false>   // MODE 0: CONV3, 1: CONV3_T (flipped taps), 2: CONV3_UP, 3: CONV3 of silu(GroupNorm(x))
 __global__ __launch_bounds__(512, 2) void conv3_k32p_kernel(const k32p_args a) {
     static_assert(!PS || (!F16 && MODE != 3), "pre-split inputs: split-precision arithmetic, no folded GroupNorm");
+    static_assert(!ONE || !F16, "one bf16 product: split-precision operands");
     const vd_gemm_desc& d = a.d;
     constexpr int BM = 128, NPIX = 256, NTH = 512;
     constexpr int NPART = F16 ? 1 : 2;
@@ -311,16 +314,19 @@ __global__ __launch_bounds__(512, 2) void conv3_k32p_kernel(const k32p_args a) {
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi) {
                 wh[mi] = __builtin_bit_cast(bf16x8, a_cur[(s * 4 + 0) * BM + mi * 16]);
-                wl[mi] = __builtin_bit_cast(bf16x8, a_cur[(s * 4 + 2) * BM + mi * 16]);
+                if constexpr (!ONE) wl[mi] = __builtin_bit_cast(bf16x8, a_cur[(s * 4 + 2) * BM + mi * 16]);
             }
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
                 const bf16x8 xh = __builtin_bit_cast(bf16x8, p_base[ni][pr * PW + ps]);
-                const bf16x8 xl = __builtin_bit_cast(bf16x8, p_base[ni][2 * PLANE + pr * PW + ps]);
+                bf16x8 xl;
+                if constexpr (!ONE) xl = __builtin_bit_cast(bf16x8, p_base[ni][2 * PLANE + pr * PW + ps]);
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi) {
-                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wl[mi], acc[ni][mi], 0, 0, 0);
-                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, wh[mi], acc[ni][mi], 0, 0, 0);
+                    if constexpr (!ONE) {
+                        acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wl[mi], acc[ni][mi], 0, 0, 0);
+                        acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, wh[mi], acc[ni][mi], 0, 0, 0);
+                    }
                     acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wh[mi], acc[ni][mi], 0, 0, 0);
                 }
             }
@@ -341,10 +347,10 @@ __global__ __launch_bounds__(512, 2) void conv3_k32p_kernel(const k32p_args a) {
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
             wh[mi] = __builtin_bit_cast(bf16x8, a_cur[(0 * 4 + 0) * BM + mi * 16]);
-            wl[mi] = __builtin_bit_cast(bf16x8, a_cur[(0 * 4 + 2) * BM + mi * 16]);
+            if constexpr (!ONE) wl[mi] = __builtin_bit_cast(bf16x8, a_cur[(0 * 4 + 2) * BM + mi * 16]);
         }
         xh[0] = __builtin_bit_cast(bf16x8, p_base[0][pr * PW + tap_col(0)]);
-        xl[0] = __builtin_bit_cast(bf16x8, p_base[0][2 * PLANE + pr * PW + tap_col(0)]);
+        if constexpr (!ONE) xl[0] = __builtin_bit_cast(bf16x8, p_base[0][2 * PLANE + pr * PW + tap_col(0)]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
@@ -355,19 +361,21 @@ __global__ __launch_bounds__(512, 2) void conv3_k32p_kernel(const k32p_args a) {
                 if (!last) {                                      // the next pixel tile (of this tap, or the first of the next tap)
                     const int ns = (ni == 3) ? s + 1 : s, nn = (ni == 3) ? 0 : ni + 1;
                     xh[nxt] = __builtin_bit_cast(bf16x8, p_base[nn][pr * PW + tap_col(ns)]);
-                    xl[nxt] = __builtin_bit_cast(bf16x8, p_base[nn][2 * PLANE + pr * PW + tap_col(ns)]);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                    if constexpr (!ONE) xl[nxt] = __builtin_bit_cast(bf16x8, p_base[nn][2 * PLANE + pr * PW + tap_col(ns)]);
+                    __builtin_amdgcn_sched_group_barrier(0x100, ONE ? 1 : 2, 0);
                 }
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi) {
-                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wl[mi], acc[ni][mi], 0, 0, 0);
-                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[cur], wh[mi], acc[ni][mi], 0, 0, 0);
+                    if constexpr (!ONE) {
+                        acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wl[mi], acc[ni][mi], 0, 0, 0);
+                        acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[cur], wh[mi], acc[ni][mi], 0, 0, 0);
+                    }
                     acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wh[mi], acc[ni][mi], 0, 0, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, ONE ? 1 : 3, 0);
                     if (ni == 3 && s < 2) {                       // this channel tile's weights are dead: fetch the next tap's
                         wh[mi] = __builtin_bit_cast(bf16x8, a_cur[((s + 1) * 4 + 0) * BM + mi * 16]);
-                        wl[mi] = __builtin_bit_cast(bf16x8, a_cur[((s + 1) * 4 + 2) * BM + mi * 16]);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                        if constexpr (!ONE) wl[mi] = __builtin_bit_cast(bf16x8, a_cur[((s + 1) * 4 + 2) * BM + mi * 16]);
+                        __builtin_amdgcn_sched_group_barrier(0x100, ONE ? 1 : 2, 0);
                     }
                 }
             }
@@ -744,13 +752,15 @@ int vd_launch_conv3_k32p(const vd_gemm_desc& d, int mode, hipStream_t st) {
 #define VD_K32P_CASE(WW, MD)                                                                                         \
     if (TW == WW && mode == MD) {                                                                                    \
         if (d.math == 2) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, true>), dim3(grid), dim3(512), 0, st, a);   \
+        else if (d.math == 3) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false, false, true>), dim3(grid), dim3(512), 0, st, a); \
         else hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false>), dim3(grid), dim3(512), 0, st, a);    \
         return 0;                                                                                                    \
     }
 #endif
 #define VD_K32P_PS(WW, MD)                                                                                           \
     if (d.b_presplit && TW == WW && mode == MD) {                                                                    \
-        hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false, true>), dim3(grid), dim3(512), 0, st, a);   \
+        if (d.math == 3) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false, true, true>), dim3(grid), dim3(512), 0, st, a); \
+        else hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false, true>), dim3(grid), dim3(512), 0, st, a); \
         return 0;                                                                                                    \
     }
     VD_K32P_PS(32, 0) VD_K32P_PS(32, 1) VD_K32P_PS(32, 2) VD_K32P_PS(16, 0) VD_K32P_PS(16, 1) VD_K32P_PS(16, 2)

@@ -43,7 +43,8 @@ struct sm_args {
 };
 
 // KH: chunk pairs (32 input channels each) per stage.  Shipped: 1 (KH = 2 halves the number of barriers and was measured 3-25 % slower).
-template <int W, int MODE, int IMGS, int KH>   // MODE 0: VD_B_CONV3, 1: VD_B_CONV3_T (flipped taps)
+// ONE (vd_gemm_desc.math = 3, opt-in bf16 mixed precision): same stages and LDS images; the fragment loop reads the hi planes only and issues hi*hi.
+template <int W, int MODE, int IMGS, int KH, bool ONE = false>   // MODE 0: VD_B_CONV3, 1: VD_B_CONV3_T (flipped taps)
 __global__ __launch_bounds__(256, 2) void conv3_sm_kernel(const sm_args a) {
     const vd_gemm_desc& d = a.d;
     constexpr int BM = 64, NTH = 256, HW = W * W, NPIX = IMGS * HW;
@@ -187,13 +188,13 @@ __global__ __launch_bounds__(256, 2) void conv3_sm_kernel(const sm_args a) {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
                 wh[set][mi] = __builtin_bit_cast(bf16x8, a_cur[(s * 4 + 0) * BM + mi * 16]);
-                wl[set][mi] = __builtin_bit_cast(bf16x8, a_cur[(s * 4 + 2) * BM + mi * 16]);
+                if constexpr (!ONE) wl[set][mi] = __builtin_bit_cast(bf16x8, a_cur[(s * 4 + 2) * BM + mi * 16]);
             }
         };
         auto load_x = [&](int k) {                               // pixel tile k = s * NI + ni of the stage
             const int s = k / NI, ni = k - s * NI;
             xh[k % XR] = __builtin_bit_cast(bf16x8, p_base[ni][pko + pr * PW + tap_col(s)]);
-            xl[k % XR] = __builtin_bit_cast(bf16x8, p_base[ni][pko + 2 * PLANE + pr * PW + tap_col(s)]);
+            if constexpr (!ONE) xl[k % XR] = __builtin_bit_cast(bf16x8, p_base[ni][pko + 2 * PLANE + pr * PW + tap_col(s)]);
         };
         load_w(0, 0);
 #pragma unroll
@@ -204,19 +205,21 @@ __global__ __launch_bounds__(256, 2) void conv3_sm_kernel(const sm_args a) {
             const int s = k / NI, ni = k - s * NI, cur = k % XR, ws = s & 1;
             if (k + XD < NT3) {
                 load_x(k + XD);
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, ONE ? 1 : 2, 0);
             }
             if (ni == 0 && s < 2) {
                 load_w(s + 1, ws ^ 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, ONE ? 2 : 4, 0);
             }
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
-                acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wl[ws][mi], acc[ni][mi], 0, 0, 0);
-                acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[cur], wh[ws][mi], acc[ni][mi], 0, 0, 0);
+                if constexpr (!ONE) {
+                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wl[ws][mi], acc[ni][mi], 0, 0, 0);
+                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[cur], wh[ws][mi], acc[ni][mi], 0, 0, 0);
+                }
                 acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wh[ws][mi], acc[ni][mi], 0, 0, 0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, ONE ? 2 : 6, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -345,7 +348,8 @@ int vd_launch_conv3_sm(const vd_gemm_desc& d, hipStream_t st) {
     // profiles/r06_conv_sm_ab.txt)
 #define VD_SM_CASE(WW, MD, IM)                                                                                   \
     if (d.OW == WW && mode == MD && imgs == IM) {                                                                \
-        hipLaunchKernelGGL((conv3_sm_kernel<WW, MD, IM, 1>), dim3(a.n_tiles), dim3(256), 0, st, a);              \
+        if (d.math == 3) hipLaunchKernelGGL((conv3_sm_kernel<WW, MD, IM, 1, true>), dim3(a.n_tiles), dim3(256), 0, st, a); \
+        else hipLaunchKernelGGL((conv3_sm_kernel<WW, MD, IM, 1>), dim3(a.n_tiles), dim3(256), 0, st, a);     \
         return 0;                                                                                                \
     }
     VD_SM_CASE(8, 0, 2) VD_SM_CASE(8, 1, 2) VD_SM_CASE(4, 0, 4) VD_SM_CASE(4, 1, 4)

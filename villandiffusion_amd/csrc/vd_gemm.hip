@@ -20,7 +20,7 @@
 bool vd_conv3_k32p_eligible(const vd_gemm_desc& d);
 int vd_launch_conv3_k32p(const vd_gemm_desc& d, int mode, hipStream_t st);
 // vd_presplit.hip: the grouped 3x3 weight gradient with both operands pre-split (LDS-DMA + transposed reads)
-int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks, hipStream_t st);
+int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks, hipStream_t st, bool one);
 // vd_conv_sm.hip: the whole-K 16x16x32 split-precision 3x3 convolution of the 8x8 / 4x4 levels (round 6)
 bool vd_conv3_sm_eligible(const vd_gemm_desc& d);
 int vd_launch_conv3_sm(const vd_gemm_desc& d, hipStream_t st);
@@ -2171,6 +2171,15 @@ extern "C" int vd_gemm_tile(const vd_gemm_desc* desc) {
         if (gemm_bx3_eligible(d) && vd_gemm1x1_k32p_pick(d)) return 19;
         return -1;
     }
+    if (d.a_packed && d.math == 3) {      // opt-in bf16 mixed precision: one hi*hi product per term -- the kernels with that switch only
+        if (bx3_eligible(d)) {
+            if (vd_conv3_sm_eligible(d)) return 20;
+            if (!bx3_big_split(d) && k32p_pick(d)) return 18;
+            return -1;
+        }
+        if (gemm_bx3_eligible(d) && vd_gemm1x1_k32p_pick(d)) return 19;
+        return -1;
+    }
     if (d.a_packed) {
         if (bx3_eligible(d)) {
             int splits, c_per;
@@ -2212,6 +2221,7 @@ extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
     VD_REQUIRE(desc != nullptr, "vd_gemm: null desc");
     vd_gemm_desc d = *desc;
     VD_REQUIRE(d.A && d.B && d.D, "vd_gemm: null operand");
+    VD_REQUIRE(d.math != 3 || d.a_packed, "vd_gemm: math = 3 (one bf16 product per term) reads the hi plane of a_packed; a_packed is NULL");
     VD_REQUIRE(d.b_presplit == 0 || (d.b_presplit == 1 && vd_gemm_tile(&d) == 18),
                "vd_gemm: a pre-split B operand (b_presplit = %d) is read by the persistent 16x16x32 convolution only (vd_gemm_tile() == 18; this problem: %d)",
                d.b_presplit, d.b_presplit == 1 ? vd_gemm_tile(&d) : 0);
@@ -2241,7 +2251,8 @@ extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
     const int tile = vd_gemm_tile(&d);
     VD_REQUIRE(tile != -1, "vd_gemm: a_packed (split-precision bf16) needs a 3x3 convolution with 8x8 / 16x16 / 32x32 outputs, "
                            "C %% 16 == 0, M >= 64, or a VD_B_PLAIN product with shared A, NP %% 128 == 0, K %% 16 == 0, M >= 64; "
-                           "a_packed_mpad = M rounded up to 128; math = 1 needs per-batch A, PLAIN / KCONTIG B, NP %% 128 == 0, K %% 16 == 0, K >= 32, M >= 64");
+                           "a_packed_mpad = M rounded up to 128; math = 1 needs per-batch A, PLAIN / KCONTIG B, NP %% 128 == 0, K %% 16 == 0, K >= 32, M >= 64; "
+                           "math = 2 / 3 need the persistent 16x16x32 kernels (vd_gemm_tile 18 / 19; math = 3 also 20)");
     VD_REQUIRE(!d.gn_ss || tile == 4 || tile == 6 || tile == 8 || tile == 12 || tile == 15 || tile == 17 || tile == 18,
                "vd_gemm: gn_ss (GroupNorm folded into the loader) needs the patch-staged 3x3 kernel (OW 16/32, C %% 8 == 0, M >= 64)");
     VD_REQUIRE(!d.pool2 || tile == 8 || tile == 12 || tile == 17 || tile == 18, "vd_gemm: pool2 needs the split-precision 3x3 kernel (VD_B_CONV3_T with a_packed)");
@@ -2371,6 +2382,7 @@ extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) {
     vd_wgrad_desc d = *desc;
     VD_REQUIRE(d.dY && d.X && d.dW, "vd_conv_wgrad: null operand");
     VD_REQUIRE(d.presplit == 0, "vd_conv_wgrad: pre-split operands (presplit = %d) are taken by the grouped launches only (vd_conv_wgrad_group_*)", d.presplit);
+    VD_REQUIRE(d.math == 0 || d.math == 1, "vd_conv_wgrad: math = %d -- one bf16 product per term (math = 3) is taken by the grouped launches only (vd_conv_wgrad_group_*)", d.math);
     VD_REQUIRE(d.T == 9 || d.T == 1, "vd_conv_wgrad: T must be 1 or 9");
     VD_REQUIRE((d.T == 1) == (d.mode == VD_B_PLAIN), "vd_conv_wgrad: T/mode mismatch");
     VD_REQUIRE(d.NP == d.OH * d.OW && d.NP % 4 == 0 && d.OW % 4 == 0, "vd_conv_wgrad: NP/OW must be multiples of 4");
@@ -2495,7 +2507,17 @@ extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) {
 // Class of a split-precision weight gradient = the kernel instantiation it runs on; only jobs of one class share a launch.
 //   3x3: 4 * W + 2 * (CONV3_UP) + (wide image)   (W = 32 / 16 / 8 / 4),   stride-2 3x3: 2000 + W (W = 16 / 8),   1x1: 1000,   0: not groupable
 //   both operands PRE-SPLIT (d.presplit == 3, round 5): 3000 + 4 * W + 2 * (CONV3_UP)   (3x3 at 8x8 / 16x16 / 32x32 outputs)
+//   math = 3 (one bf16 product per term): VD_WG_ONE + the class of the same problem at math = 1, where that class runs on a kernel with the
+//   one-product switch (wgrad_ps_group_kernel, wgrad_k32_group_kernel, wgrad1x1_wide_group_kernel); else 0.  A launch never mixes arithmetics.
+constexpr int VD_WG_ONE = 10000;
 static int wgrad_group_class(const vd_wgrad_desc& d) {
+    if (d.math == 3) {
+        vd_wgrad_desc d1 = d;
+        d1.math = 1;
+        const int c = wgrad_group_class(d1);
+        const int v = c ? vd_conv_wgrad_group_variant(c) : 0;
+        return (v == 3000 || v == 32 || v == 256) ? VD_WG_ONE + c : 0;
+    }
     if (d.math != 1 || d.splits != 0 || d.tile != 0) return 0;
     if (d.presplit != 0) {
         const bool up = d.mode == VD_B_CONV3_UP;
@@ -2524,6 +2546,7 @@ extern "C" int64_t vd_conv_wgrad_group_job_bytes(void) { return (int64_t)sizeof(
 // Which kernel vd_conv_wgrad_group_launch runs for a class: 9 = wgrad9_group_kernel (all nine taps per workgroup), 32 = wgrad_k32_group_kernel
 // (16x16x32 one-tap-row kernel, the default where it applies), 0 = wgrad_bx3_group_kernel / wgrad1x1_bx3_group_kernel (profiling names, tests).
 extern "C" int vd_conv_wgrad_group_variant(int cls) {
+    if (cls > VD_WG_ONE) return vd_conv_wgrad_group_variant(cls - VD_WG_ONE);      // same kernel family, one product per term
     if (cls >= 3000) return 3000;                   // wgrad_ps_group_kernel (pre-split operands)
     if (wgrad9_class(cls)) return 9;
     if (cls == 1000) return wgrad1x1_wide_enabled() ? 256 : 0;
@@ -2537,10 +2560,11 @@ extern "C" int vd_conv_wgrad_group_variant(int cls) {
 extern "C" int vd_conv_wgrad_group_plan(const vd_wgrad_desc* descs, int n, void* table_out, int64_t* ws_floats, int* blocks, int* rblocks) {
     VD_REQUIRE(descs && n > 0 && table_out && ws_floats && blocks && rblocks, "vd_conv_wgrad_group_plan: bad args");
     const int cls = wgrad_group_class(descs[0]);
-    VD_REQUIRE(cls != 0, "vd_conv_wgrad_group_plan: job 0 is not a split-precision (math = 1) 3x3 / 1x1 weight gradient");
+    VD_REQUIRE(cls != 0, "vd_conv_wgrad_group_plan: job 0 is not a groupable split-precision (math = 1) or one-product (math = 3) 3x3 / 1x1 weight gradient");
     vd_wgrad_job* jobs = reinterpret_cast<vd_wgrad_job*>(table_out);
-    const bool one = cls == 1000;
-    const bool nine = cls < 3000 && wgrad9_class(cls);           // one workgroup (512 threads, one per CU) per tile produces all nine taps
+    const int bcls = cls > VD_WG_ONE ? cls - VD_WG_ONE : cls;     // the geometry (tiles, K-steps, targets) of a math = 3 class is its math = 1 class's
+    const bool one = bcls == 1000;
+    const bool nine = bcls < 3000 && wgrad9_class(bcls);           // one workgroup (512 threads, one per CU) per tile produces all nine taps
     const bool wide1 = one && wgrad1x1_wide_enabled();           // 1x1: BM x 256 tiles, 32-pixel K-steps, one 512-thread workgroup per CU
     auto job_base = [&](const vd_wgrad_desc& d) -> int64_t {
         if (wide1) return (int64_t)vd_cdiv(d.M, wgrad1x1_wide_bm(d)) * vd_cdiv(d.C, 256);
@@ -2570,7 +2594,7 @@ extern "C" int vd_conv_wgrad_group_plan(const vd_wgrad_desc* descs, int n, void*
     static const int cap9 = getenv("VD_WGRAD9_KCAP") ? atoi(getenv("VD_WGRAD9_KCAP")) : 128;
     static const int tw = getenv("VD_W1X1_WIDE_TARGET") ? atoi(getenv("VD_W1X1_WIDE_TARGET")) : 256;
     static const int capw = getenv("VD_W1X1_WIDE_KCAP") ? atoi(getenv("VD_W1X1_WIDE_KCAP")) : 64;
-    const bool k32 = cls >= 3000 || (!one && !nine && cls != 4 * 4 + 0 && !(cls & 1) && wgrad_k32_enabled());      // two workgroups per CU: 512 resident slots
+    const bool k32 = bcls >= 3000 || (!one && !nine && bcls != 4 * 4 + 0 && !(bcls & 1) && wgrad_k32_enabled());      // two workgroups per CU: 512 resident slots
     // (512 = the resident slots; 448 / 384 measured 0.15 ms per config-#2 step faster, same box, three interleaved rounds: the small classes get
     // longer K ranges and fewer slabs, the large ones are capped at 128 steps either way -- profiles/r04_wgrad_k32_target.txt)
     static const int t32 = getenv("VD_WGRAD_K32_TARGET") ? atoi(getenv("VD_WGRAD_K32_TARGET")) : 448;
@@ -2637,12 +2661,42 @@ extern "C" int vd_conv_wgrad_group_launch(const void* dev_table, int n, int cls,
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(blocks);
     switch (cls) {
+        case VD_WG_ONE + 1000: {
+            VD_REQUIRE(wgrad1x1_wide_enabled(), "vd_conv_wgrad_group_launch: class %d needs the wide 1x1 kernel (VD_W1X1_WIDE)", cls);
+            static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<true>),
+                                                                hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
+            VD_REQUIRE(attr1 == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
+            hipLaunchKernelGGL(wgrad1x1_wide_group_kernel<true>, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
+            break;
+        }
+        case VD_WG_ONE + 4 * 32 + 0: case VD_WG_ONE + 4 * 32 + 2: case VD_WG_ONE + 4 * 16 + 0: case VD_WG_ONE + 4 * 16 + 2:
+        case VD_WG_ONE + 4 * 8 + 0: case VD_WG_ONE + 4 * 8 + 2: {
+            VD_REQUIRE(vd_conv_wgrad_group_variant(cls) == 32, "vd_conv_wgrad_group_launch: class %d needs the 16x16x32 kernel (VD_WGRAD_K32)", cls);
+            const int wc = (cls - VD_WG_ONE) / 4;
+            const bool up = (cls - VD_WG_ONE) & 2;
+            if (wc == 32) {
+                if (up) hipLaunchKernelGGL((wgrad_k32_group_kernel<32, 2, true>), grid, dim3(NT), 0, st, jobs, n);
+                else hipLaunchKernelGGL((wgrad_k32_group_kernel<32, 0, true>), grid, dim3(NT), 0, st, jobs, n);
+            } else if (wc == 16) {
+                if (up) hipLaunchKernelGGL((wgrad_k32_group_kernel<16, 2, true>), grid, dim3(NT), 0, st, jobs, n);
+                else hipLaunchKernelGGL((wgrad_k32_group_kernel<16, 0, true>), grid, dim3(NT), 0, st, jobs, n);
+            } else {
+                if (up) hipLaunchKernelGGL((wgrad_k32_group_kernel<8, 2, true>), grid, dim3(NT), 0, st, jobs, n);
+                else hipLaunchKernelGGL((wgrad_k32_group_kernel<8, 0, true>), grid, dim3(NT), 0, st, jobs, n);
+            }
+            break;
+        }
+        case VD_WG_ONE + 3000 + 4 * 32: case VD_WG_ONE + 3000 + 4 * 16: case VD_WG_ONE + 3000 + 4 * 8: case VD_WG_ONE + 3000 + 4 * 32 + 2:
+        case VD_WG_ONE + 3000 + 4 * 16 + 2: case VD_WG_ONE + 3000 + 4 * 8 + 2:
+            VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - VD_WG_ONE - 3000) / 4, (cls - VD_WG_ONE - 3000) & 2, blocks, st, true) == 0,
+                       "vd_conv_wgrad_group_launch: no pre-split kernel for class %d", cls);
+            break;
         case 1000:
             if (wgrad1x1_wide_enabled()) {
-                static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel),
+                static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<>),
                                                                    hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
                 VD_REQUIRE(attr == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
-                hipLaunchKernelGGL(wgrad1x1_wide_group_kernel, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
+                hipLaunchKernelGGL(wgrad1x1_wide_group_kernel<>, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
             } else {
                 hipLaunchKernelGGL(wgrad1x1_bx3_group_kernel, grid, dim3(NT), 0, st, jobs, n);
             }
@@ -2667,7 +2721,7 @@ extern "C" int vd_conv_wgrad_group_launch(const void* dev_table, int n, int cls,
 #undef VD_WG_K32
         case 4 * 4 + 0: hipLaunchKernelGGL((wgrad_bx3_group_kernel<4, 0>), grid, dim3(NT), 0, st, jobs, n); break;
         case 3000 + 4 * 32: case 3000 + 4 * 16: case 3000 + 4 * 8: case 3000 + 4 * 32 + 2: case 3000 + 4 * 16 + 2: case 3000 + 4 * 8 + 2:
-            VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - 3000) / 4, (cls - 3000) & 2, blocks, st) == 0,
+            VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - 3000) / 4, (cls - 3000) & 2, blocks, st, false) == 0,
                        "vd_conv_wgrad_group_launch: no pre-split kernel for class %d", cls);
             break;
         case 2000 + 33: hipLaunchKernelGGL((wgrad_bx3_group_kernel<32, 4, true>), grid, dim3(NT), 0, st, jobs, n); break;

@@ -58,7 +58,8 @@ struct g32p_args {
 // items to load, split and store per MFMA (the weights, which arrive by LDS-DMA and cost no VALU, double instead).  The kernel is bound by the
 // VALU issue of that split, repeated for every m-tile of a pixel tile (6 x for the 256 -> 768 projection); with BM = 256 it is repeated 3 x, and
 // layers of 256 output channels convert every activation exactly once.  Taken when M % 256 == 0.
-template <bool F16, int BM = 128>
+// ONE (vd_gemm_desc.math = 3, opt-in bf16 mixed precision): the split-precision operands as they are, hi planes only: one bf16 MFMA (hi*hi) per term.
+template <bool F16, int BM = 128, bool ONE = false>
 __global__ __launch_bounds__(512, 2) void gemm1x1_k32p_kernel(const g32p_args a) {
     const vd_gemm_desc& d = a.d;
     constexpr int NPIX = 128 * 256 / BM, NTH = 512;
@@ -216,26 +217,28 @@ __global__ __launch_bounds__(512, 2) void gemm1x1_k32p_kernel(const g32p_args a)
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
             wh[mi] = __builtin_bit_cast(bf16x8, a_cur[mi * 16]);
-            wl[mi] = __builtin_bit_cast(bf16x8, a_cur[2 * BM + mi * 16]);
+            if constexpr (!ONE) wl[mi] = __builtin_bit_cast(bf16x8, a_cur[2 * BM + mi * 16]);
         }
         xh[0] = __builtin_bit_cast(bf16x8, p_cur[0]);
-        xl[0] = __builtin_bit_cast(bf16x8, p_cur[2 * PL]);
+        if constexpr (!ONE) xl[0] = __builtin_bit_cast(bf16x8, p_cur[2 * PL]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
             const int cur = ni & 1, nxt = cur ^ 1;
             if (ni < 3) {
                 xh[nxt] = __builtin_bit_cast(bf16x8, p_cur[(ni + 1) * 4]);
-                xl[nxt] = __builtin_bit_cast(bf16x8, p_cur[2 * PL + (ni + 1) * 4]);
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                if constexpr (!ONE) xl[nxt] = __builtin_bit_cast(bf16x8, p_cur[2 * PL + (ni + 1) * 4]);
+                __builtin_amdgcn_sched_group_barrier(0x100, ONE ? 1 : 2, 0);
             }
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi) {
-                acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wl[mi], acc[ni][mi], 0, 0, 0);
-                acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[cur], wh[mi], acc[ni][mi], 0, 0, 0);
+                if constexpr (!ONE) {
+                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wl[mi], acc[ni][mi], 0, 0, 0);
+                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[cur], wh[mi], acc[ni][mi], 0, 0, 0);
+                }
                 acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[cur], wh[mi], acc[ni][mi], 0, 0, 0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, ONE ? 4 : 12, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -398,6 +401,8 @@ int vd_launch_gemm1x1_k32p(const vd_gemm_desc& d, hipStream_t st) {
     a.n_tiles = a.tiles_m * (d.N / (big_m ? 128 : 256));
     const int grid = a.n_tiles < n_cu ? ((a.n_tiles + 7) & ~7) : n_cu;
     if (d.math == 2) hipLaunchKernelGGL((gemm1x1_k32p_kernel<true, 128>), dim3(grid), dim3(512), 0, st, a);
+    else if (d.math == 3 && big_m) hipLaunchKernelGGL((gemm1x1_k32p_kernel<false, 256, true>), dim3(grid), dim3(512), 0, st, a);
+    else if (d.math == 3) hipLaunchKernelGGL((gemm1x1_k32p_kernel<false, 128, true>), dim3(grid), dim3(512), 0, st, a);
     else if (big_m) hipLaunchKernelGGL((gemm1x1_k32p_kernel<false, 256>), dim3(grid), dim3(512), 0, st, a);
     else hipLaunchKernelGGL((gemm1x1_k32p_kernel<false, 128>), dim3(grid), dim3(512), 0, st, a);
     return 0;

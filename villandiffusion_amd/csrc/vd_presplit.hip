@@ -369,11 +369,16 @@ __device__ __forceinline__ void tr_read(s16x4& dst, unsigned addr) {
 __device__ __forceinline__ void lgkm_wait4(s16x4& a, s16x4& b, s16x4& c, s16x4& e) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(e)::"memory");
 }
+__device__ __forceinline__ void lgkm_wait2(s16x4& a, s16x4& b) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)::"memory");
+}
 __device__ __forceinline__ bf16x8 cat8(const s16x4& lo4, const s16x4& hi4) {
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-template <int W, int MODE>   // W: 8 | 16 | 32 (output width = pixels per image row); MODE 0: VD_B_CONV3, 2: VD_B_CONV3_UP
+// ONE (vd_wgrad_desc.math = 3, opt-in bf16 mixed precision): the DMA stages are unchanged; the lo parts are not read (no ds_read_b64_tr_b16 of them)
+// and one bf16 MFMA (hi * hi) runs per product term.
+template <int W, int MODE, bool ONE = false>   // W: 8 | 16 | 32 (output width = pixels per image row); MODE 0: VD_B_CONV3, 2: VD_B_CONV3_UP
 __device__ __forceinline__ void wgrad_ps_body(const vd_wgrad_desc& d, int ksteps_per_split, int gx, int gy, int lin, u32x4* lds) {
     constexpr int ROWS = 32 / W, OPR = W / 8, CT = 64;
     constexpr int PS_ST_U = ps_stage_units(MODE);
@@ -518,35 +523,46 @@ __device__ __forceinline__ void wgrad_ps_body(const vd_wgrad_desc& d, int ksteps
         // all 16 dY reads + the first X fragment pair, one wait; then per (tap, channel tile): the NEXT pair's 4 reads are issued in front of the 12 MFMAs
         // of the current one and waited for behind them (192 matrix cycles cover the LDS round trip)
         s16x4 ar[4][2][2];                           // [m tile][part][h]   (immediates: m tile = 2 octets = 2048 B, part = 512 B)
-        tr_read<SOFF + 0 * 2048>(ar[0][0][0], a_addr[0]); tr_read<SOFF + 0 * 2048>(ar[0][0][1], a_addr[1]);
-        tr_read<SOFF + 0 * 2048 + 512>(ar[0][1][0], a_addr[0]); tr_read<SOFF + 0 * 2048 + 512>(ar[0][1][1], a_addr[1]);
-        tr_read<SOFF + 1 * 2048>(ar[1][0][0], a_addr[0]); tr_read<SOFF + 1 * 2048>(ar[1][0][1], a_addr[1]);
-        tr_read<SOFF + 1 * 2048 + 512>(ar[1][1][0], a_addr[0]); tr_read<SOFF + 1 * 2048 + 512>(ar[1][1][1], a_addr[1]);
-        tr_read<SOFF + 2 * 2048>(ar[2][0][0], a_addr[0]); tr_read<SOFF + 2 * 2048>(ar[2][0][1], a_addr[1]);
-        tr_read<SOFF + 2 * 2048 + 512>(ar[2][1][0], a_addr[0]); tr_read<SOFF + 2 * 2048 + 512>(ar[2][1][1], a_addr[1]);
-        tr_read<SOFF + 3 * 2048>(ar[3][0][0], a_addr[0]); tr_read<SOFF + 3 * 2048>(ar[3][0][1], a_addr[1]);
-        tr_read<SOFF + 3 * 2048 + 512>(ar[3][1][0], a_addr[0]); tr_read<SOFF + 3 * 2048 + 512>(ar[3][1][1], a_addr[1]);
+        if constexpr (ONE) {                         // hi parts only
+            tr_read<SOFF + 0 * 2048>(ar[0][0][0], a_addr[0]); tr_read<SOFF + 0 * 2048>(ar[0][0][1], a_addr[1]);
+            tr_read<SOFF + 1 * 2048>(ar[1][0][0], a_addr[0]); tr_read<SOFF + 1 * 2048>(ar[1][0][1], a_addr[1]);
+            tr_read<SOFF + 2 * 2048>(ar[2][0][0], a_addr[0]); tr_read<SOFF + 2 * 2048>(ar[2][0][1], a_addr[1]);
+            tr_read<SOFF + 3 * 2048>(ar[3][0][0], a_addr[0]); tr_read<SOFF + 3 * 2048>(ar[3][0][1], a_addr[1]);
+        } else {
+            tr_read<SOFF + 0 * 2048>(ar[0][0][0], a_addr[0]); tr_read<SOFF + 0 * 2048>(ar[0][0][1], a_addr[1]);
+            tr_read<SOFF + 0 * 2048 + 512>(ar[0][1][0], a_addr[0]); tr_read<SOFF + 0 * 2048 + 512>(ar[0][1][1], a_addr[1]);
+            tr_read<SOFF + 1 * 2048>(ar[1][0][0], a_addr[0]); tr_read<SOFF + 1 * 2048>(ar[1][0][1], a_addr[1]);
+            tr_read<SOFF + 1 * 2048 + 512>(ar[1][1][0], a_addr[0]); tr_read<SOFF + 1 * 2048 + 512>(ar[1][1][1], a_addr[1]);
+            tr_read<SOFF + 2 * 2048>(ar[2][0][0], a_addr[0]); tr_read<SOFF + 2 * 2048>(ar[2][0][1], a_addr[1]);
+            tr_read<SOFF + 2 * 2048 + 512>(ar[2][1][0], a_addr[0]); tr_read<SOFF + 2 * 2048 + 512>(ar[2][1][1], a_addr[1]);
+            tr_read<SOFF + 3 * 2048>(ar[3][0][0], a_addr[0]); tr_read<SOFF + 3 * 2048>(ar[3][0][1], a_addr[1]);
+            tr_read<SOFF + 3 * 2048 + 512>(ar[3][1][0], a_addr[0]); tr_read<SOFF + 3 * 2048 + 512>(ar[3][1][1], a_addr[1]);
+        }
         s16x4 br[2][2][2];                           // [buffer][part][h]
         auto b_reads = [&](int k, s16x4 (&dst)[2][2]) {      // combination k = (tap order o = k >> 1, channel tile ct = k & 1); centre tap first
             const int o = k >> 1, ct = k & 1;
             const int sx = o == 0 ? 1 : (o == 1 ? 0 : 2);
             if (ct == 0) {
                 tr_read<0>(dst[0][0], b_st[SB][sx][0]); tr_read<0>(dst[0][1], b_st[SB][sx][1]);
-                tr_read<B_PART>(dst[1][0], b_st[SB][sx][0]); tr_read<B_PART>(dst[1][1], b_st[SB][sx][1]);
+                if constexpr (!ONE) { tr_read<B_PART>(dst[1][0], b_st[SB][sx][0]); tr_read<B_PART>(dst[1][1], b_st[SB][sx][1]); }
             } else {
                 tr_read<B_CT>(dst[0][0], b_st[SB][sx][0]); tr_read<B_CT>(dst[0][1], b_st[SB][sx][1]);
-                tr_read<B_CT + B_PART>(dst[1][0], b_st[SB][sx][0]); tr_read<B_CT + B_PART>(dst[1][1], b_st[SB][sx][1]);
+                if constexpr (!ONE) { tr_read<B_CT + B_PART>(dst[1][0], b_st[SB][sx][0]); tr_read<B_CT + B_PART>(dst[1][1], b_st[SB][sx][1]); }
             }
         };
         b_reads(0, br[0]);
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) lgkm_wait4(ar[mt][0][0], ar[mt][0][1], ar[mt][1][0], ar[mt][1][1]);
-        lgkm_wait4(br[0][0][0], br[0][0][1], br[0][1][0], br[0][1][1]);
+        for (int mt = 0; mt < 4; ++mt) {
+            if constexpr (ONE) lgkm_wait2(ar[mt][0][0], ar[mt][0][1]);
+            else lgkm_wait4(ar[mt][0][0], ar[mt][0][1], ar[mt][1][0], ar[mt][1][1]);
+        }
+        if constexpr (ONE) lgkm_wait2(br[0][0][0], br[0][0][1]);
+        else lgkm_wait4(br[0][0][0], br[0][0][1], br[0][1][0], br[0][1][1]);
         bf16x8 ah[4], al[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             ah[mt] = cat8(ar[mt][0][0], ar[mt][0][1]);
-            al[mt] = cat8(ar[mt][1][0], ar[mt][1][1]);
+            if constexpr (!ONE) al[mt] = cat8(ar[mt][1][0], ar[mt][1][1]);
         }
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
@@ -555,16 +571,22 @@ __device__ __forceinline__ void wgrad_ps_body(const vd_wgrad_desc& d, int ksteps
             const int sx = o == 0 ? 1 : (o == 1 ? 0 : 2);
             if (k < 5) b_reads(k + 1, br[cur ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
-            const bf16x8 xh = cat8(br[cur][0][0], br[cur][0][1]), xl = cat8(br[cur][1][0], br[cur][1][1]);
+            const bf16x8 xh = cat8(br[cur][0][0], br[cur][0][1]);
             // same product order per accumulator as wgrad_k32_body: lo * hi, hi * lo, hi * hi, the four m tiles inside each product
+            if constexpr (!ONE) {
+                const bf16x8 xl = cat8(br[cur][1][0], br[cur][1][1]);
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], xh, acc[mt][ct][sx], 0, 0, 0);
+                for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], xh, acc[mt][ct][sx], 0, 0, 0);
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xl, acc[mt][ct][sx], 0, 0, 0);
+                for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xl, acc[mt][ct][sx], 0, 0, 0);
+            }
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xh, acc[mt][ct][sx], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (k < 5) lgkm_wait4(br[cur ^ 1][0][0], br[cur ^ 1][0][1], br[cur ^ 1][1][0], br[cur ^ 1][1][1]);
+            if (k < 5) {
+                if constexpr (ONE) lgkm_wait2(br[cur ^ 1][0][0], br[cur ^ 1][0][1]);
+                else lgkm_wait4(br[cur ^ 1][0][0], br[cur ^ 1][0][1], br[cur ^ 1][1][0], br[cur ^ 1][1][1]);
+            }
         }
     };
 
@@ -625,14 +647,14 @@ __device__ __forceinline__ void wgrad_ps_body(const vd_wgrad_desc& d, int ksteps
     }
 }
 
-template <int W, int MODE>
+template <int W, int MODE, bool ONE = false>
 __global__ __launch_bounds__(256, 2) void wgrad_ps_group_kernel(const vd_wgrad_job* __restrict__ jobs, int n_jobs) {
     __shared__ u32x4 lds[ps_lds_units(MODE)];       // ONE LDS object (a second one beside an LDS-DMA target makes hipcc wait vmcnt(0) before every ds_read)
     const vd_wgrad_job* __restrict__ jb = jobs + wgrad_find_job(jobs, n_jobs, blockIdx.x, false);
     const int lin = blockIdx.x - jb->first_block;
     if (lin >= jb->gx * jb->gy) return;            // padding blocks between jobs
     const vd_wgrad_desc d = jb->d;
-    wgrad_ps_body<W, MODE>(d, jb->ks_per, jb->gx, jb->gy, lin, lds);
+    wgrad_ps_body<W, MODE, ONE>(d, jb->ks_per, jb->gx, jb->gy, lin, lds);
 }
 
 }  // namespace
@@ -725,8 +747,8 @@ extern "C" int vd_groupnorm_bwd_presplit(const float* dy, const float* x, const 
     return 0;
 }
 
-// vd_gemm.hip's grouped launch (class 3000 + 4 W + 2 * upsample-fused): both operands pre-split
-int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks, hipStream_t st) {
+// vd_gemm.hip's grouped launch (class 3000 + 4 W + 2 * upsample-fused): both operands pre-split; one: one bf16 product per term (math = 3)
+int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks, hipStream_t st, bool one) {
     const vd_wgrad_job* jb = reinterpret_cast<const vd_wgrad_job*>(jobs);
     // 4.5 KB of (unused) dynamic LDS on top of the kernel's 76 KB: ONE workgroup per CU instead of two (2 x 80.5 KB > 160 KB).  Two of them hold a CU's whole
     // LDS and register file for ~90 us at a time, and the backward pass on the main stream -- latency-bound 8x8 / 4x4 kernels, GroupNorm passes -- only gets a CU
@@ -737,8 +759,10 @@ int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks,
     static const int pad = getenv("VD_WGRAD_PS_LDS_PAD") ? atoi(getenv("VD_WGRAD_PS_LDS_PAD")) : 4608;
 #define VD_WG_PS(WW)                                                                                                \
     case WW:                                                                                                        \
-        if (up) hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 2>), dim3(blocks), dim3(256), pad, st, jb, n);        \
-        else hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 0>), dim3(blocks), dim3(256), pad, st, jb, n);           \
+        if (one && up) hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 2, true>), dim3(blocks), dim3(256), pad, st, jb, n); \
+        else if (one) hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 0, true>), dim3(blocks), dim3(256), pad, st, jb, n);  \
+        else if (up) hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 2>), dim3(blocks), dim3(256), pad, st, jb, n);         \
+        else hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 0>), dim3(blocks), dim3(256), pad, st, jb, n);            \
         return 0;
     switch (W) {
         VD_WG_PS(32) VD_WG_PS(16) VD_WG_PS(8)

@@ -8,7 +8,8 @@
 // 0.75 x (128 x 256) of the bytes per FLOP.  Eight waves (2 x 4, wave tile BM/2 x 64), one workgroup per CU; a K-step is 32 pixels (4 octets;
 // NP % 8 == 0, an octet never straddles images), the 64 / 48 KB stage is double-buffered: one barrier per K-step.
 //     As[buf][part][octet 0..3][BM + 2]     Bs[buf][part][octet 0..3][258]       (octet stride + 2 units: as wgrad1x1_bx3_body)
-template <int BM>
+// ONE (vd_wgrad_desc.math = 3, opt-in bf16 mixed precision): the same (hi, lo) stages, hi fragments only: one bf16 MFMA (ah * bh) per product term.
+template <int BM, bool ONE = false>
 __device__ __forceinline__ void wgrad1x1_wide_body(const vd_wgrad_desc& d, int ksteps_per_split, int gx, int gy, int lin) {
     constexpr int BC = 256;
     constexpr int LDA_ = BM + 2, LDB_ = BC + 2;
@@ -119,16 +120,19 @@ __device__ __forceinline__ void wgrad1x1_wide_body(const vd_wgrad_desc& d, int k
 #pragma unroll
                 for (int mi = 0; mi < WM; ++mi) {
                     ah[mi] = __builtin_bit_cast(bf16x8, a_base[(2 * kk) * LDA_ + mi * 32]);
-                    al[mi] = __builtin_bit_cast(bf16x8, a_base[(4 + 2 * kk) * LDA_ + mi * 32]);
+                    if constexpr (!ONE) al[mi] = __builtin_bit_cast(bf16x8, a_base[(4 + 2 * kk) * LDA_ + mi * 32]);
                 }
 #pragma unroll
                 for (int ni = 0; ni < 2; ++ni) {
                     const bf16x8 bh = __builtin_bit_cast(bf16x8, b_base[(2 * kk) * LDB_ + ni * 32]);
-                    const bf16x8 bl = __builtin_bit_cast(bf16x8, b_base[(4 + 2 * kk) * LDB_ + ni * 32]);
+                    bf16x8 bl;
+                    if constexpr (!ONE) bl = __builtin_bit_cast(bf16x8, b_base[(4 + 2 * kk) * LDB_ + ni * 32]);
 #pragma unroll
                     for (int mi = 0; mi < WM; ++mi) {
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh, acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl, acc[mi][ni], 0, 0, 0);
+                        if constexpr (!ONE) {
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh, acc[mi][ni], 0, 0, 0);
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl, acc[mi][ni], 0, 0, 0);
+                        }
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh, acc[mi][ni], 0, 0, 0);
                     }
                 }
@@ -157,13 +161,14 @@ __device__ __forceinline__ void wgrad1x1_wide_body(const vd_wgrad_desc& d, int k
 }
 
 // BM is a property of the JOB (layers with at most 128 output channels take the 128-row tile), so one launch serves mixed groups.
+template <bool ONE = false>
 __global__ __launch_bounds__(512, 2) void wgrad1x1_wide_group_kernel(const vd_wgrad_job* __restrict__ jobs, int n_jobs) {
     const vd_wgrad_job* __restrict__ jb = jobs + wgrad_find_job(jobs, n_jobs, blockIdx.x, false);
     const int lin = blockIdx.x - jb->first_block;
     if (lin >= jb->gx * jb->gy) return;
     const vd_wgrad_desc d = jb->d;
-    if (d.M > 128) wgrad1x1_wide_body<256>(d, jb->ks_per, jb->gx, jb->gy, lin);
-    else wgrad1x1_wide_body<128>(d, jb->ks_per, jb->gx, jb->gy, lin);
+    if (d.M > 128) wgrad1x1_wide_body<256, ONE>(d, jb->ks_per, jb->gx, jb->gy, lin);
+    else wgrad1x1_wide_body<128, ONE>(d, jb->ks_per, jb->gx, jb->gy, lin);
 }
 
 constexpr int W1X1_WIDE_LDS = 2 * (2 * 4 * (256 + 2) + 2 * 4 * (256 + 2)) * 16;      // 132 096 B (BM = 256)

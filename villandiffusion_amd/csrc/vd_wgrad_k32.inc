@@ -15,7 +15,9 @@
 //  * Units are XOR-swizzled inside their group of eight rows (row ^ 2 * octet): the eight lanes of a ds_write_b128 service group
 //    (four octets of two rows) and the 16-lane halves of a ds_read_b128 group (two k-groups of 16 rows) then each hit distinct bank quads
 //    with an octet stride that is a multiple of 16 units.
-template <int W, int MODE>   // W: 8 | 16 | 32 (output width = pixels per image row); MODE 0: CONV3, 2: CONV3_UP (X is the half-resolution source)
+// ONE (vd_wgrad_desc.math = 3, opt-in bf16 mixed precision): the stages are staged as (hi, lo) all the same; the loop reads the hi fragments only and
+// issues ah * xh -- one bf16 MFMA per product term.
+template <int W, int MODE, bool ONE = false>   // W: 8 | 16 | 32 (output width = pixels per image row); MODE 0: CONV3, 2: CONV3_UP (X is the half-resolution source)
 __device__ __forceinline__ void wgrad_k32_body(const vd_wgrad_desc& d, int ksteps_per_split, int gx, int gy, int lin) {
     constexpr int ROWS = 32 / W;                   // image rows per K-step
     constexpr int OPR = W / 8;                     // octets per row
@@ -150,7 +152,7 @@ __device__ __forceinline__ void wgrad_k32_body(const vd_wgrad_desc& d, int kstep
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 ah[mt] = __builtin_bit_cast(bf16x8, as_[mt * 16]);
-                al[mt] = __builtin_bit_cast(bf16x8, as_[4 * 128 + mt * 16]);
+                if constexpr (!ONE) al[mt] = __builtin_bit_cast(bf16x8, as_[4 * 128 + mt * 16]);
             }
             // both channel tiles' fragments and their neighbour exchanges are issued up front; the centre tap (which needs no exchange)
             // multiplies first, so the ds_bpermute round trips of the shifted fragments hide under 24 MFMAs
@@ -158,25 +160,28 @@ __device__ __forceinline__ void wgrad_k32_body(const vd_wgrad_desc& d, int kstep
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
                 fh[ct][1] = bs_[ct * 16];
-                fl[ct][1] = bs_[4 * CT + ct * 16];
+                if constexpr (!ONE) fl[ct][1] = bs_[4 * CT + ct * 16];
             }
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
                 shifted(fh[ct][1], fh[ct][0], fh[ct][2]);
-                shifted(fl[ct][1], fl[ct][0], fl[ct][2]);
+                if constexpr (!ONE) shifted(fl[ct][1], fl[ct][0], fl[ct][2]);
             }
 #pragma unroll
             for (int o = 0; o < 3; ++o) {
                 const int sx = o == 0 ? 1 : (o == 1 ? 0 : 2);
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
-                    const bf16x8 xh = __builtin_bit_cast(bf16x8, fh[ct][sx]), xl = __builtin_bit_cast(bf16x8, fl[ct][sx]);
+                    const bf16x8 xh = __builtin_bit_cast(bf16x8, fh[ct][sx]);
                     // the three products of a tile are a dependency chain on its accumulator: walk the four m tiles inside each product, so that
                     // an MFMA's accumulator was written four issues (64 cycles) earlier, not by the instruction in front of it
+                    if constexpr (!ONE) {
+                        const bf16x8 xl = __builtin_bit_cast(bf16x8, fl[ct][sx]);
 #pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], xh, acc[mt][ct][sx], 0, 0, 0);
+                        for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], xh, acc[mt][ct][sx], 0, 0, 0);
 #pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xl, acc[mt][ct][sx], 0, 0, 0);
+                        for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xl, acc[mt][ct][sx], 0, 0, 0);
+                    }
 #pragma unroll
                     for (int mt = 0; mt < 4; ++mt) acc[mt][ct][sx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xh, acc[mt][ct][sx], 0, 0, 0);
                 }
@@ -273,13 +278,13 @@ __global__ __launch_bounds__(NT, 2) void wgrad_k32_kernel(const vd_wgrad_desc d,
     wgrad_k32_body<W, MODE>(d, ksteps_per_split, gridDim.x, gridDim.y, blockIdx.x + gridDim.x * blockIdx.y);
 }
 
-template <int W, int MODE>
+template <int W, int MODE, bool ONE = false>
 __global__ __launch_bounds__(NT, 2) void wgrad_k32_group_kernel(const vd_wgrad_job* __restrict__ jobs, int n_jobs) {
     const vd_wgrad_job* __restrict__ jb = jobs + wgrad_find_job(jobs, n_jobs, blockIdx.x, false);
     const int lin = blockIdx.x - jb->first_block;
     if (lin >= jb->gx * jb->gy) return;            // padding blocks between jobs
     const vd_wgrad_desc d = jb->d;
-    wgrad_k32_body<W, MODE>(d, jb->ks_per, jb->gx, jb->gy, lin);
+    wgrad_k32_body<W, MODE, ONE>(d, jb->ks_per, jb->gx, jb->gy, lin);
 }
 
 // Round 3 (one register set, loads one step ahead): 0.93-0.97 x of wgrad_bx3_body on seven of the eight layer shapes of config #2 -- the halved LDS

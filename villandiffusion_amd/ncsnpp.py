@@ -254,6 +254,8 @@ class NCSNppModel(UNet2DModel):
         return buf
 
     def _run_forward(self, x, t, save):
+        if self.conv_math == "bf16":
+            raise NotImplementedError("NCSN++: conv_math = 'bf16' (one bf16 product per term) is not supported by this model; use 'bf16x3', 'f16' or 'f32'")
         dev = self._dev
         B, _, S, _ = x.shape
         st = SimpleNamespace(B=B, tape=[], marks={})

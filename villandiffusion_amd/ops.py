@@ -256,9 +256,10 @@ def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bs
     d.pad = pad
     d.pool2 = int(pool2)
     d.math = math_mode
-    a_packed16 = None
-    if isinstance(a_packed, tuple):            # (split-precision operand, f16 operand): opt-in mixed precision, decided per problem below
-        a_packed, a_packed16 = a_packed
+    a_packed16, alt_math = None, 2
+    if isinstance(a_packed, tuple):            # (split-precision operand, single-product operand[, math]): opt-in mixed precision, decided per problem below
+        a_packed, a_packed16, *rest = a_packed # (f16: the f16 operand, math 2; bf16: the split-precision operand again, math 3)
+        alt_math = rest[0] if rest else 2
     if a_packed is not None:
         d.a_packed, d.a_packed_mpad = a_packed.data_ptr(), (M + 127) // 128 * 128
     d.gn_ss = _p(gn_ss)
@@ -282,17 +283,17 @@ def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bs
     elif FORCE_WS is not None:                 # diagnostic builds only (tools/k32p_stamps.py: the stamp buffer travels in the unused ws pointer)
         d.ws = FORCE_WS.data_ptr()
     global LAST_GEMM_TILE, LAST_GEMM_MATH
-    if a_packed16 is not None and gn_part is None:
-        # f16 operands are read by the persistent 16x16x32 kernels only (vd_gemm_tile 18 / 19 with math = 2); every other problem keeps the
-        # split-precision operand
-        d.a_packed, d.math = a_packed16.data_ptr(), 2
-        if lib.vd_gemm_tile(C.byref(d)) not in (18, 19):
+    if a_packed16 is not None and (gn_part is None or alt_math == 3):
+        # single-product operands are read by the persistent 16x16x32 kernels only (vd_gemm_tile 18 / 19 with math = 2; 18 / 19 / 20 with
+        # math = 3), the library answers -1 for every other problem: that keeps the split-precision operand
+        d.a_packed, d.math = a_packed16.data_ptr(), alt_math
+        if lib.vd_gemm_tile(C.byref(d)) not in ((18, 19) if alt_math == 2 else (18, 19, 20)):
             d.a_packed, d.math = a_packed.data_ptr(), math_mode
     LAST_GEMM_MATH = d.math
     LAST_GEMM_TILE = lib.vd_gemm_tile(C.byref(d))            # kernel family the library picks for this problem (tests assert on it)
     global ACT_OUT_WRITTEN
     ACT_OUT_WRITTEN = False
-    if act_out is not None and gn_ss is not None and a_packed16 is None:
+    if act_out is not None and gn_ss is not None and (a_packed16 is None or alt_math == 3):
         # side output of the persistent kernel's GroupNorm-folding loader (vd_gemm_desc.act_out): taken only where that kernel runs the problem
         d.act_out, d.act_bstride = act_out.data_ptr(), _img(act_out)[4]
         if lib.vd_gemm_tile(C.byref(d)) == 18:
@@ -328,7 +329,8 @@ def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bs
     elif tl == 19:
         # (the 256 x 128 tile where M % 256 == 0: vd_launch_gemm1x1_k32p; symbol names as rocprofv3 prints them)
         big = d.math != 2 and M % 256 == 0 and N % 128 == 0 and os.environ.get("VD_G32P_BM256", "1") != "0"
-        name = "gemm1x1_k32p_kernel<true, 128>" if d.math == 2 else f"gemm1x1_k32p_kernel<false, {256 if big else 128}>"
+        name = ("gemm1x1_k32p_kernel<true, 128>" if d.math == 2 else
+                f"gemm1x1_k32p_kernel<false, {256 if big else 128}{', true' if d.math == 3 else ''}>")
     elif tl in (9, 11, 13):
         name = "gemm_bx3_persist_kernel" if tl == 11 else f"gemm_bx3_kernel<{512 if tl == 13 else 256}>"
     elif tl == 17:
@@ -336,11 +338,12 @@ def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bs
         name = f"conv3_k32_kernel<{d.OW}, {md}>"
     elif tl == 18:          # the persistent kernel: template width 16 (16x16 images) or 32 (8-row x 32-column segments of any image); image width beside it
         md = (3 if gn_ss is not None else 0) if b_mode == B_CONV3 else (1 if b_mode == B_CONV3_T else 2)
-        name = (f"conv3_k32p_kernel<{16 if d.OW == 16 else 32}, {md}, true, true, {'true' if d.math == 2 else 'false'}, {'true' if d.b_presplit else 'false'}>"
+        name = (f"conv3_k32p_kernel<{16 if d.OW == 16 else 32}, {md}, true, true, {'true' if d.math == 2 else 'false'}, {'true' if d.b_presplit else 'false'}"
+                + (", true>" if d.math == 3 else ">")
                 + (f"@{d.OW}" if d.OW > 32 else ""))
     elif tl == 20:          # the whole-K kernel of the 8x8 / 4x4 levels
         imgs = 2 if d.OW == 8 else 4
-        name = f"conv3_sm_kernel<{d.OW}, {1 if b_mode == B_CONV3_T else 0}, {imgs}, 1>"
+        name = f"conv3_sm_kernel<{d.OW}, {1 if b_mode == B_CONV3_T else 0}, {imgs}, 1{', true' if d.math == 3 else ''}>"
     elif tl in (8, 12, 15, 16):
         md = (3 if gn_ss is not None else 0) if b_mode == B_CONV3 else (1 if b_mode == B_CONV3_T else (4 if b_mode == B_CONV3_S2 else 2))
         name = f"conv3_bx3_kernel<{d.OW if d.OW <= 64 else 128}, {md}, {4 if tl == 15 else 2}, {256 if tl == 8 else 512}, 2>"
@@ -606,6 +609,9 @@ def wgrad_desc(dy, x, dw2d, mode, ws=None, accumulate=False, splits=0, tile=0, p
     return d
 
 
+WGRAD_ONE = 10000       # class offset of the one-product (math = 3) grouped weight gradients (vd_conv_wgrad_group_class)
+
+
 def wgrad_group_class(d: WgradDesc) -> int:
     """Kernel class of a split-precision weight gradient for the grouped launch (0: not groupable -> conv_wgrad)."""
     return int(L.load().vd_conv_wgrad_group_class(C.byref(d)))
@@ -670,10 +676,11 @@ def upload_table(host: torch.Tensor, device, after=None) -> torch.Tensor:
 
 def conv_wgrad_group(descs: Sequence[WgradDesc], device):
     """All `descs` (one kernel class, see wgrad_group_class) in ONE compute launch + ONE fixed-order slab reduction.  The device job
-    table is planned by the library and uploaded once per distinct set of operand addresses (steady-state training repeats them)."""
+    table is planned by the library and uploaded once per distinct set of operand addresses (steady-state training repeats them).
+    One-product (math = 3) jobs have classes of their own: a launch never mixes arithmetics (UNet2DModel.wgrad queues per class)."""
     lib = _lib()
     n = len(descs)
-    key = tuple((d.dY, d.X, d.dW, d.M, d.C, d.T, d.nb, d.NP, d.H, d.W, d.OH, d.OW, d.mode, d.accumulate, d.dy_bstride, d.x_bstride, d.presplit)
+    key = tuple((d.dY, d.X, d.dW, d.M, d.C, d.T, d.nb, d.NP, d.H, d.W, d.OH, d.OW, d.mode, d.accumulate, d.dy_bstride, d.x_bstride, d.presplit, d.math)
                 for d in descs)
     ent = _WG_CACHE.get(key)
     ws = _WG_WS.get(device)
@@ -700,7 +707,15 @@ def conv_wgrad_group(descs: Sequence[WgradDesc], device):
     flops = sum(2.0 * d.M * d.C * d.T * d.nb * d.NP for d in descs)
     nbytes = sum(4.0 * (d.nb * d.M * d.NP + d.nb * d.C * d.H * d.W + d.M * d.C * d.T) for d in descs)
     var = lib.vd_conv_wgrad_group_variant(ent["cls"])
-    if ent["cls"] >= 3000:                                       # both operands pre-split: LDS-DMA + transposed reads (vd_presplit.hip)
+    if ent["cls"] > WGRAD_ONE:                                   # one bf16 product per term (math = 3): the ONE instantiations
+        bc = ent["cls"] - WGRAD_ONE
+        if bc >= 3000:
+            name = f"wgrad_ps_group_kernel<{(bc - 3000) // 4}, {(bc - 3000) & 2}, true>(+group_reduce)"
+        elif bc == 1000:
+            name = "wgrad1x1_wide_group_kernel<true>(+group_reduce)"
+        else:
+            name = f"wgrad_k32_group_kernel<{bc // 4}, {bc & 2}, true>(+group_reduce)"
+    elif ent["cls"] >= 3000:                                     # both operands pre-split: LDS-DMA + transposed reads (vd_presplit.hip)
         name = f"wgrad_ps_group_kernel<{(ent['cls'] - 3000) // 4}, {(ent['cls'] - 3000) & 2}>(+group_reduce)"
     elif ent["cls"] > 2000:                                      # stride-2 3x3 classes (2000 + output width; 2033: 32-pixel segments of wide outputs)
         name = "wgrad_bx3_group_kernel<32, 4, true>(+group_reduce)" if ent["cls"] == 2033 else f"wgrad_bx3_group_kernel<{ent['cls'] - 2000}, 4, false>(+group_reduce)"

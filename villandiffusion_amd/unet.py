@@ -46,8 +46,8 @@ def _ensure_path(root: nn.Module, parts: Sequence[str]) -> nn.Module:
 
 # ----------------------------------------------------------------------------------------------------------- layers
 CONV_MATH_DEFAULT = os.environ.get("VILLAN_CONV_MATH", "bf16x3")
-if CONV_MATH_DEFAULT not in ("bf16x3", "f32", "f16"):
-    raise ValueError(f"VILLAN_CONV_MATH must be 'bf16x3', 'f32' or 'f16', got {CONV_MATH_DEFAULT!r}")
+if CONV_MATH_DEFAULT not in ("bf16x3", "f32", "f16", "bf16"):
+    raise ValueError(f"VILLAN_CONV_MATH must be 'bf16x3', 'f32', 'f16' or 'bf16', got {CONV_MATH_DEFAULT!r}")
 
 
 class _PackedConvWeights:
@@ -118,15 +118,27 @@ class _PackedConvWeights:
 
 
 def _split(net) -> bool:
-    """Contractions on the bf16 matrix cores: "bf16x3" (default), and "f16" -- the opt-in mixed-precision mode (round 4), which ADDITIONALLY runs
-    the full-size 3x3 / 1x1 forward and input-gradient contractions as single f16 products (everything else as in "bf16x3")."""
-    return getattr(net, "conv_math", "f32") in ("bf16x3", "f16")
+    """Contractions on the bf16 matrix cores: "bf16x3" (default), and the two opt-in mixed-precision modes, which ADDITIONALLY run some
+    contractions as single products: "f16" (round 4) the full-size 3x3 / 1x1 forward and input gradients as f16 products, "bf16" those AND the
+    weight gradients as hi*hi bf16 products of the split-precision operands (everything else as in "bf16x3")."""
+    return getattr(net, "conv_math", "f32") in ("bf16x3", "f16", "bf16")
 
 
-def _with_f16(net, pk, key, bwd):
-    """In "f16" mode the operand handed to ops.gemm is the pair (split-precision operand, f16 operand); ops.gemm picks per problem."""
-    if pk is None or getattr(net, "conv_math", "f32") != "f16":
+def _pairs(net) -> bool:
+    """Does the arithmetic read bf16 (hi, lo) operands -- pre-split images, the folded GroupNorm loader's pairs, the pre-split weight gradients?
+    "bf16x3" reads both parts; "bf16" reads the same operands and uses the hi parts only, so it takes every pre-split / folded path "bf16x3" takes.
+    ("f16" reads f16 planes: none of these paths.)"""
+    return getattr(net, "conv_math", "f32") in ("bf16x3", "bf16")
+
+
+def _with_mixed(net, pk, key, bwd):
+    """In a mixed-precision mode the operand handed to ops.gemm is (split-precision operand, single-product operand, vd_gemm_desc.math):
+    "f16": the f16 operand, math 2; "bf16": the split-precision operand itself (its hi plane), math 3.  ops.gemm picks per problem."""
+    mode = getattr(net, "conv_math", "f32")
+    if pk is None or mode not in ("f16", "bf16"):
         return pk
+    if mode == "bf16":
+        return (pk, pk, 3)
     p16 = getattr(net, "_packed16", None)
     if p16 is None:
         p16 = net._packed16 = _PackedConvWeights(net, f16=True)
@@ -141,7 +153,7 @@ def _bx3_packed(net, prefix, bwd, M, Cc, OH, OW, mode):
     pk = getattr(net, "_packed", None)
     if pk is None:
         pk = net._packed = _PackedConvWeights(net)
-    return _with_f16(net, pk.view(prefix, bwd), prefix, bwd)
+    return _with_mixed(net, pk.view(prefix, bwd), prefix, bwd)
 
 
 def _bx3_packed_1x1(net, key, bwd, M, K, NP, nb=None):
@@ -151,7 +163,7 @@ def _bx3_packed_1x1(net, key, bwd, M, K, NP, nb=None):
     pk = getattr(net, "_packed", None)
     if pk is None:
         pk = net._packed = _PackedConvWeights(net)
-    return _with_f16(net, pk.view(key, bwd), key, bwd)
+    return _with_mixed(net, pk.view(key, bwd), key, bwd)
 
 
 def _amath(net, M, K, NP) -> int:
@@ -191,7 +203,7 @@ class _Conv:
         here, the forward convolution copies (hi, lo) units too instead of splitting every element once per tap row and channel tile."""
         net = self.net
         B, _, H, W = h.shape
-        if (self.mode != B_CONV3_UP or not net.us_fwd_presplit or not getattr(net, "presplit", False) or net.conv_math != "bf16x3" or H != W
+        if (self.mode != B_CONV3_UP or not net.us_fwd_presplit or not getattr(net, "presplit", False) or not _pairs(net) or H != W
                 or not ops.conv_presplit_ok(B, self.cin, self.cout, 2 * H, 2 * W, B_CONV3_UP)
                 or (save and not (net.group_wgrad and ops.wgrad_presplit_ok(B, self.cin, self.cout, 2 * H, B_CONV3_UP)))):
             return h
@@ -208,7 +220,7 @@ class _Conv:
             net.wgrad(dy_ps, x, net.G[self.prefix + ".weight"].view(self.cout, self.cin * 9), self.mode, pad=self.pad, math_mode=1)
             if dout_ps is not None:
                 dout = dout_ps                                # the input gradient copies (hi, lo) units too
-        elif (self.mode == B_CONV3_UP and getattr(net, "presplit", False) and net.conv_math == "bf16x3" and net.group_wgrad
+        elif (self.mode == B_CONV3_UP and getattr(net, "presplit", False) and _pairs(net) and net.group_wgrad
               and dout.shape[2] == dout.shape[3] and ops.wgrad_presplit_ok(dout.shape[0], self.cin, self.cout, dout.shape[3], B_CONV3_UP)):
             # Upsample2D's convolution: its input is a block output (f32), so the image is packed on the weight-gradient stream -- two small passes
             # off the critical path for the LDS-DMA kernel (the 256 -> 256 layer at 32x32 outputs is 0.42 ms per step on the converting kernel)
@@ -368,7 +380,7 @@ class _Resnet:
         all four convolution launches (conv1 / conv2 forward and input gradient) go to the persistent 16x16x32 kernel -- the only reader of
         pre-split images -- and both weight gradients have a pre-split grouped kernel.  Decided per (block, batch, image size), cached."""
         net = self.net
-        if not getattr(net, "presplit", False) or net.conv_math != "bf16x3" or not net.group_wgrad or H != W:
+        if not getattr(net, "presplit", False) or not _pairs(net) or not net.group_wgrad or H != W:
             return False
         key = (B, H, W)
         ok = self._ps_cache.get(key)
@@ -412,7 +424,7 @@ class _Resnet:
             else:
                 self.conv2.fwd(h1, out, residual=x, gn_ss=ss2)
             return None
-        if save and net.fold_gn_train and fuse and net.conv_math == "bf16x3" and not net.defer_gn_fwd and ops.gn_fusable(x, self.cout) \
+        if save and net.fold_gn_train and fuse and _pairs(net) and not net.defer_gn_fwd and ops.gn_fusable(x, self.cout) \
                 and self.cin % 32 == 0 and self.cout % 32 == 0 and self.cin * H * W // net.groups <= 12288 \
                 and self.cout * H * W // net.groups <= 12288:
             # Training forward without a normalise pass (round 4): the persistent convolution's loader applies GroupNorm + SiLU (as in the no-grad
@@ -978,6 +990,9 @@ class UNet2DModel(nn.Module):
         self._pk_jobs = []
         # "bf16x3": eligible 3x3 convolutions (forward and stride-1 input gradient at 8x8 / 16x16 / 32x32) run on the bf16 matrix
         # cores as hi*hi + hi*lo + lo*hi with f32 accumulation (~1e-5 of the exact result); "f32": everything on the exact f32 MFMA.
+        # Opt-in mixed precision: "f16" (see _split) and "bf16" -- one hi*hi product per term wherever a kernel has that switch
+        # (vd_gemm_desc.math = 3 / vd_wgrad_desc.math = 3: the persistent and whole-K convolutions, the persistent 1x1 kernel and the grouped
+        # weight gradients); the other contractions stay "bf16x3".
         self.conv_math = CONV_MATH_DEFAULT
         self._packed: Optional[_PackedConvWeights] = None
         self._packed16: Optional[_PackedConvWeights] = None     # f16 operands of the opt-in mixed-precision mode (conv_math = "f16")
@@ -1092,6 +1107,10 @@ class UNet2DModel(nn.Module):
     def wgrad(self, dy, x, dw2d, mode, pad=0, math_mode=0):
         if math_mode == 1 and self.group_wgrad:
             d = ops.wgrad_desc(dy, x, dw2d, mode, None, accumulate=True, pad=pad, math_mode=1)
+            if self.conv_math == "bf16":                      # one bf16 product per term where a grouped kernel has that switch (its own class)
+                d3 = ops.wgrad_desc(dy, x, dw2d, mode, None, accumulate=True, pad=pad, math_mode=3)
+                if ops.wgrad_group_class(d3):
+                    d = d3
             cls = ops.wgrad_group_class(d)
             if cls:
                 self._wg_jobs.setdefault(cls, []).append((d, dy, x))
@@ -1471,7 +1490,7 @@ class UNet2DModel(nn.Module):
             nxt = sv[-1]
             if nxt[0] == "res" and isinstance(nxt[2][5], ops.PreSplit):
                 return ops.presplit_empty(shape, dev)
-            if (nxt[0] == "us" and self.presplit and self.conv_math == "bf16x3" and self.group_wgrad
+            if (nxt[0] == "us" and self.presplit and _pairs(self) and self.group_wgrad
                     and ops.wgrad_presplit_ok(shape[0], nxt[1].cin, nxt[1].cout, shape[3], B_CONV3_UP)):
                 return ops.presplit_empty(shape, dev)            # (the upsampler's weight gradient reads it; its input gradient reads f32)
             return None
