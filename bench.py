@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark of the backdoored-diffusion hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one optimiser step of the poisoned fine-tune loop at per-GPU batch 128 on synthetic CIFAR10-shaped data
 (config #2 of BASELINE.json): GPU trigger stamping -> q-sample+backdoor target -> UNet fwd -> MSE -> UNet bwd ->
 (RCCL all-reduce) -> clip + Adam.  Inputs (uint8 dataset, weights) are resident in HBM before the timed region.
-After the timed region the same process measures 1000-step DDPM sampling (second half of the metric), times the
-MFMA kernels of one extra step with HIP events (roofline) and, on rank 0 at N=1, the CPU oracle (cpu_baseline).
+A plain run sets up, warms up, times the K steps (the headline `value` / `ms_per_step`) and prints the line.  With --full the
+same process then also times the multi-rank schedule and the exact-f32 / f16 arithmetics, measures 1000-step DDPM sampling
+(second half of the metric) and the secondary samplers, times the MFMA kernels of one extra step with HIP events (roofline)
+and, on rank 0 at N=1, the CPU oracle (cpu_baseline, parity); --config selects the secondary lines (--full only).
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -78,8 +80,19 @@ def parse():
                     help="after the timed steps, write what they computed as DIR/<name>.npy (float32, rank 0): train_loss = the loss of the last "
                          "timed step, train_params = the parameters after it, sample_images = the images of the timed DDPM sampling leg; an array "
                          "above its element budget is a fixed seeded sample of its flattened elements (under 64 MB in all).  Same arguments, "
-                         "same inputs: two builds can be compared file for file (e.g. DIR = bench_outputs/<build>)")
-    return ap.parse_args()
+                         "same inputs: two builds can be compared file for file (e.g. DIR = bench_outputs/<build>).  Without --full the run "
+                         "still takes the sampling leg and the training legs that precede it in a --full run: the files are the same either way")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline steps, run every other leg: multi-rank schedule, exact-f32 / f16 arithmetics, DDPM-1000 and secondary "
+                         "sampling, roofline, CPU oracle and parity (each --no-* flag drops one), the per-kernel side file (VD_BENCH_DETAIL), and "
+                         "the --config / --mode sample lines.  Off: a plain run times the K steps and prints the line")
+    args = ap.parse_args()
+    if not args.full:
+        needs = [f for f, on in (("--config " + args.config, args.config != "cifar10"), ("--mode sample", args.mode == "sample"),
+                                 ("--ddp-path", args.ddp_path), ("--eager-sample", args.eager_sample), ("--cpu-true-1000", args.cpu_true_1000)) if on]
+        if needs:
+            ap.error(f"{', '.join(needs)}: only with --full")
+    return args
 
 
 def cpu_baseline(batch: int = 128, n_steps: int = 3, state_dict=None, gpu_side=None, true_1000: bool = False):
@@ -517,6 +530,11 @@ def main():
             dist.barrier()
 
     do_train, do_sample = args.mode in ("all", "train"), args.mode in ("all", "sample") and args.sample_images > 0
+    # A plain run stops after the timed steps; --full runs every leg below.  --dump-outputs also needs the images of the sampling leg, and they are the images a --full
+    # run samples: the training legs that run between the timed steps and the sampler in a --full run (they move the weights, the Adam
+    # state and the timestep generator) then run before it here too.
+    do_sample = do_sample and (args.full or bool(args.dump_outputs))
+    pre_sample = args.full or do_sample
     log(f"setup done (world={world}, B={B}, mode={args.mode}); warm-up {args.warmup} steps")
     train_ips = dt = final_loss = None
     host_submit_ms = host_sync_ms = None
@@ -549,20 +567,21 @@ def main():
             dumps["train_params"] = dump_array(net.flat_param, DUMP_PARAMS_ELEMS, 1)
         log(f"train: {train_ips:.1f} img/s ({1e3 * dt / args.steps:.2f} ms/step), loss {final_loss:.4f}")
         # host side of one step: time until the last launch of a step has been SUBMITTED (queue drained first) vs until it has run
-        sub = []
-        for i in range(3):
-            torch.cuda.synchronize()
-            h0 = time.perf_counter()
-            one_step(args.warmup + args.steps + i)
-            h1 = time.perf_counter()
-            torch.cuda.synchronize()
-            sub.append((h1 - h0, time.perf_counter() - h0))
-        host_submit_ms, host_sync_ms = 1e3 * min(a for a, _ in sub), 1e3 * min(b for _, b in sub)
-        log(f"host: one step submitted in {host_submit_ms:.2f} ms, finished in {host_sync_ms:.2f} ms (drained queue)")
+        if pre_sample:
+            sub = []
+            for i in range(3):
+                torch.cuda.synchronize()
+                h0 = time.perf_counter()
+                one_step(args.warmup + args.steps + i)
+                h1 = time.perf_counter()
+                torch.cuda.synchronize()
+                sub.append((h1 - h0, time.perf_counter() - h0))
+            host_submit_ms, host_sync_ms = 1e3 * min(a for a, _ in sub), 1e3 * min(b for _, b in sub)
+            log(f"host: one step submitted in {host_submit_ms:.2f} ms, finished in {host_sync_ms:.2f} ms (drained queue)")
 
         # ---- the MULTI-RANK schedule on this one GPU (reference VillanDiffusion.py:440, 1161-1166): what rank 0 of an 8-GPU run
         #      executes minus the wire time -- a size-1 RCCL communicator, one all-reduce per gradient bucket fired from the backward pass ----
-        if world == 1 and not args.no_ddp_path:
+        if pre_sample and world == 1 and not args.no_ddp_path:
             # RCCL prints its version banner / INFO lines through C stdio: they must not land on the stdout that carries the ONE JSON line.
             # Its debug file takes what honours NCCL_DEBUG_FILE; fd 1 points at stderr for the length of the leg and C stdio is flushed before it
             # is restored (the banner sat in libc's buffer until exit and came out AFTER the JSON line on the first run of this leg).
@@ -612,7 +631,7 @@ def main():
                 os.close(saved_fd1)
 
         # ---- the same K steps with every contraction on the exact-f32 MFMA (reported beside the headline, not as `value`) ----
-        if net.conv_math != "f32" and not args.no_exact:
+        if pre_sample and net.conv_math != "f32" and not args.no_exact:
             mode0, net.conv_math = net.conv_math, "f32"
             for i in range(2):
                 one_step(i)
@@ -634,7 +653,7 @@ def main():
         # ---- ... and in the opt-in mixed-precision mode (one f16 product per term in the full-size 3x3 / 1x1 forward and input-gradient
         # contractions, loss scaling in the trainer): the reference trains this config under fp16 autocast (VillanDiffusion.py:260-264).
         # Reported beside the headline, never as `value`. ----
-        if net.conv_math == "bf16x3" and not args.no_f16:
+        if pre_sample and net.conv_math == "bf16x3" and not args.no_f16:
             net.conv_math = "f16"
             for i in range(3):
                 one_step(i)
@@ -706,7 +725,7 @@ def main():
             net.sampler_graph = True
             sample_eager = {"images_per_sec": round(world * n_img / s_eager, 4), "seconds": round(s_eager, 2)}
             log(f"sample (eager launches): {sample_eager}")
-        if net.conv_math == "bf16x3" and not args.no_f16 and n_img >= 4 * B:      # the same loop in the f16 mode on 4 chunks (one round of streams)
+        if args.full and net.conv_math == "bf16x3" and not args.no_f16 and n_img >= 4 * B:      # the same loop in the f16 mode on 4 chunks (one round of streams)
             net.conv_math = "f16"
             init_full, init = init, init[:4 * B]
             s16 = timed_sampling()
@@ -719,7 +738,7 @@ def main():
         from villandiffusion_amd.pipelines import DDIMPipeline, PNDMPipeline
         from villandiffusion_amd.schedulers import DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
         secondary = {}
-        for tag, mk, pcls, nst in (() if args.no_secondary else
+        for tag, mk, pcls, nst in (() if args.no_secondary or not args.full else
                                    (("ddim50", lambda: DDIMScheduler(clip_sample=False), DDIMPipeline, 50),
                                     ("dpm_solver_pp_o2_20", lambda: DPMSolverMultistepScheduler(), PNDMPipeline, 20),
                                     ("unipc20", lambda: UniPCMultistepScheduler(), PNDMPipeline, 20))):
@@ -747,7 +766,7 @@ def main():
         log(f"secondary samplers (img/s): {secondary}")
 
     roofline, kernels, sample_kernels = None, None, None
-    if not args.no_roofline and do_train:
+    if args.full and not args.no_roofline and do_train:
         ws0, net.wgrad_stream = net.wgrad_stream, False   # per-launch durations: no weight-gradient kernels running beside the bracketed launch
         sc0, net.sc_stream = net.sc_stream, False         # ... and no shortcut 1x1 on the auxiliary stream
         for _ in range(2):                       # every rank runs the step (it contains the all-reduce); rank 0 reports
@@ -759,7 +778,7 @@ def main():
         barrier()
         if rank == 0:
             kernels = summarise(rec)
-    if not args.no_roofline and do_sample:
+    if args.full and not args.no_roofline and do_sample:
         g0, net.sampler_graph = net.sampler_graph, False          # events bracket eager launches
         sched.device_rng_seed = 99 + rank
         xs = init[:B]
@@ -843,7 +862,7 @@ def main():
         return o.images, torch.equal(sch.timesteps.cpu(), ref_timesteps) and sch.timesteps.dtype == torch.int64
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
         cpu, parity = cpu_baseline(args.cpu_batch, args.cpu_steps, state_dict=sd,
                                    gpu_side={"train": gpu_train_side, "sample": gpu_sample_side}, true_1000=args.cpu_true_1000)
@@ -875,7 +894,7 @@ def main():
                        "train": "BASELINE config #2: poison_rate 0.1, trigger BOX_14, target HAT, SDE-VP psi=1 sde, per-GPU batch %d, Adam + clip 1.0" % B,
                        "sampling": "%d-step DDPM, %d images/GPU in chunks of %d, %d chunks at a time on their own streams / HIP graphs"
                                    % (args.sample_steps, args.sample_images, B, min(args.sample_streams, max(1, -(-args.sample_images // B)))),
-                       "global_batch": B * world, "image": "3x32x32", "parallelism": f"dp{world}", "mode": args.mode},
+                       "global_batch": B * world, "image": "3x32x32", "parallelism": f"dp{world}", "mode": args.mode, "full": args.full},
             "exact_f32_mode": None if exact is None else {k: exact[k] for k in ("train_images_per_sec", "ms_per_step")},
             "f16_mode": None if f16 is None else {k: f16[k] for k in ("train_images_per_sec", "ms_per_step", "sample_ddpm1000_images_per_sec", "loss_scale") if k in f16},
             "sample_ddpm1000_images_per_sec": None if sample_ips is None else round(sample_ips, 4),
@@ -899,23 +918,24 @@ def main():
         if sample_ips is not None:
             out[f"sample_frac_of_{key}_peak"] = round(sample_ips * FWD_GFLOP_PER_IMG * args.sample_steps / 1e3 / (peak * world), 4)
         # everything that does not fit a short line (per-kernel tables of the training and the sampler step, selection rules, notes, RCCL's
-        # communicator lines) goes to a side file and to stderr: the driver keeps only the tail of stdout, and the ONE line must survive it
-        detail = dict(out)
-        detail.update({"roofline": roofline, "roofline_largest_flops": roofline_by_flops, "train_step_kernels": kernels,
-                       "sampler_step_kernels": sample_kernels, "exact_f32_mode": exact, "f16_mode": f16, "ddp_path": ddp_path, "sample_eager_launches": sample_eager,
-                       "process_group": ranks_seen,
-                       "dtype_note": ("f32 tensors and accumulation; 3x3 / 1x1 convolutions and the attention contractions (forward, input and weight "
-                                      "gradients) as hi*hi + hi*lo + lo*hi over bf16 halves on the bf16 MFMA (~1e-5 of exact f32 per contraction; the "
-                                      "reference trains this config under fp16 autocast); stride-2 convolutions, linears, conv_in / conv_out on the "
-                                      "exact f32 MFMA") if split else "every contraction on the f32-input MFMA (exact f32)"})
-        path = os.environ.get("VD_BENCH_DETAIL", os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
-        try:
-            os.makedirs(os.path.dirname(path), exist_ok=True)
-            with open(path, "w") as f:
-                json.dump(detail, f)
-            out["detail_file"] = os.path.relpath(path, ROOT)
-        except OSError as e:
-            log(f"detail file not written: {e}")
+        # communicator lines) goes to a side file and to stderr: a reader may keep only the tail of stdout, and the ONE line must survive it
+        if args.full:
+            detail = dict(out)
+            detail.update({"roofline": roofline, "roofline_largest_flops": roofline_by_flops, "train_step_kernels": kernels,
+                           "sampler_step_kernels": sample_kernels, "exact_f32_mode": exact, "f16_mode": f16, "ddp_path": ddp_path,
+                           "sample_eager_launches": sample_eager, "process_group": ranks_seen,
+                           "dtype_note": ("f32 tensors and accumulation; 3x3 / 1x1 convolutions and the attention contractions (forward, input and weight "
+                                          "gradients) as hi*hi + hi*lo + lo*hi over bf16 halves on the bf16 MFMA (~1e-5 of exact f32 per contraction; the "
+                                          "reference trains this config under fp16 autocast); stride-2 convolutions, linears, conv_in / conv_out on the "
+                                          "exact f32 MFMA") if split else "every contraction on the f32-input MFMA (exact f32)"})
+            path = os.environ.get("VD_BENCH_DETAIL", os.path.join(ROOT, "bench_outputs", "bench_detail.json"))
+            try:
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                with open(path, "w") as f:
+                    json.dump(detail, f)
+                out["detail_file"] = os.path.relpath(path, ROOT)
+            except OSError as e:
+                log(f"detail file not written: {e}")
         for tag, rows in (("train", kernels), ("sampler", sample_kernels)):
             for k in (rows or [])[:12]:
                 log(f"{tag:7s} {k['ms']:8.3f} ms {k['launches']:4d}x {k['avg_us']:8.1f} us  {k['bound']:4s} frac {k['frac']:.3f}  {k['kernel']}")

@@ -289,3 +289,28 @@ def test_dump_outputs_writes_what_the_timed_steps_computed(tmp_path):
     assert par.shape == (1 << 23,) and img.shape == (128, 3, 32, 32)          # 35.7 M parameters: a fixed sample; the images whole
     assert np.isfinite(par).all() and np.isfinite(img).all()
     assert sum(os.path.getsize(out / n) for n in os.listdir(out)) < 64e6
+
+
+# ---- a plain run times the K steps and nothing else; every other leg runs with --full ----
+def test_legs_beside_the_headline_are_refused_without_full():
+    r = _run_bench(["--config", "ldm64", "--mode", "sample", "--ddp-path", "--eager-sample", "--cpu-true-1000"], {}, timeout=120)
+    assert r.returncode == 2 and "only with --full" in r.stderr, r.stderr[-2000:]
+    for flag in ("--config ldm64", "--mode sample", "--ddp-path", "--eager-sample", "--cpu-true-1000"):
+        assert flag in r.stderr, flag
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_nothing_else(tmp_path):
+    detail = tmp_path / "detail.json"
+    r = _run_bench(["--steps", "3", "--warmup", "1"], {"VD_BENCH_DETAIL": str(detail)}, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "train imgs/sec + 1000-step DDPM sample imgs/sec, CIFAR10 bs128" and d["unit"] == "train images/s"
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 128 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16x3/f32" and d["config"]["full"] is False
+    for k in ("host_submit_ms_per_step", "ddp_path_ms_per_step", "exact_f32_mode", "f16_mode", "sample_ddpm1000_images_per_sec",
+              "sample_secondary_images_per_sec", "roofline", "top_kernels", "cpu_baseline", "parity"):
+        assert d[k] is None, k
+    assert "detail_file" not in d and not detail.exists()

@@ -141,7 +141,7 @@ def test_bench_gpus_flag_runs_two_ranks_end_to_end():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--sample-steps", "20", "--no-secondary",
-                        "--no-exact"], env=env, capture_output=True, text=True, timeout=800)
+                        "--no-exact", "--full"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) < 4096
