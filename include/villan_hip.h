@@ -124,7 +124,7 @@ typedef struct vd_gemm_desc {
     int32_t pad_h, pad_w;    /* VD_B_CONVG only: zero padding on each side                                              */
     int32_t act;             /* 0: none; 1: D = max(D, 0) after every other epilogue term (BasicConv2d = conv + folded BatchNorm + ReLU).
                                 Honoured by the exact-f32 gather / plain kernels only (a_packed == NULL, math == 0); else VD_EINVAL */
-    float* gn_part;          /* optional OUTPUT of the 16x16x32 split-precision 3x3 convolution (vd_gemm_tile() == 17, else VD_EINVAL):
+    float* gn_part;          /* optional OUTPUT of the persistent 16x16x32 3x3 convolution (vd_gemm_tile() == 18, else VD_EINVAL):
                                 [B][NP / 256][M][2] = (sum, sum of squares) of the FINAL result (after bias / rowadd / residual) of channel m
                                 over each 256-pixel tile -- the GroupNorm that follows (ResnetBlock2D: conv1 -> norm2) gets its statistics
                                 from vd_groupnorm_stats_from_partials() instead of a read of the whole tensor.  Fixed-order sums.           */
@@ -148,7 +148,7 @@ int64_t vd_gemm_ws_floats(const vd_gemm_desc* desc);
  * convolution kernel with 128x128 / 128x256 tiles, 5: plain GEMM kernel, 7: direct 3x3 convolution for <= 4 output
  * channels, 8 / 9 / 10: split-precision bf16 3x3 convolution / plain product (a_packed) / activation product (math = 1), 11: the persistent
  * variant of 9 (grids of >= 1024 tiles), 12 / 15 / 16: the 128 x 256 / 128 x 512 / split 128 x 256 tiles of 8, 13: the 128 x 256 tile of 9,
- * 17: the 16x16x32-MFMA 3x3 convolution (32-channel K-steps, 128 x 256 tile), 18: its persistent variant (LDS-DMA weight stages, 8 x 32 pixel
+ * 18: the persistent 16x16x32-MFMA 3x3 convolution (32-channel K-steps, 128 x 256 tiles, LDS-DMA weight stages, 8 x 32 pixel
  * segments of images of any size), 19: the persistent 16x16x32 kernel for 9's problems, 20 (round 6): the whole-K 16x16x32 kernel of the 8x8 level
  * (and of 4x4 grids that fill the chip): 64 channels x 2 | 4 whole images per workgroup, no split-K workspace, f32 input, VD_B_CONV3 / VD_B_CONV3_T,
  * bias / rowadd / residual / accumulate; its sums run over all channels in one chain, so it agrees with the split kernels (8 / 16) to the path's
@@ -227,7 +227,8 @@ int vd_groupnorm_bwd_presplit(const float* dy, const float* x, const float* mean
  *   launch : the two launches.  Deterministic (fixed reduction order); results agree with vd_conv_wgrad to summation order. */
 int vd_conv_wgrad_group_class(const vd_wgrad_desc* desc);
 int64_t vd_conv_wgrad_group_job_bytes(void);
-/* Kernel family a class runs on: 9 = all nine taps per workgroup (plain 3x3 at 16x16 / 32x32), 32 = opt-in 16x16x32 one-tap-row kernel, 0 = default.
+/* Kernel family a class runs on: 32 = the 16x16x32 one-tap-row kernel (plain / upsample-fused 3x3 at 8x8 .. 32x32), 256 = the wide 1x1 kernel,
+ * 3000 = the pre-split kernel, 0 = the three-copy 32x32x16 kernel (4x4, wide images, stride 2).
  * A math = 3 class (10000 + the math = 1 class) runs on the same family as its math = 1 class, one product per term. */
 int vd_conv_wgrad_group_variant(int cls);
 int vd_conv_wgrad_group_plan(const vd_wgrad_desc* descs, int n, void* table_out, int64_t* ws_floats, int* blocks, int* rblocks);

@@ -1,6 +1,5 @@
 """The 8x8 / 4x4 3x3 convolutions of config #2 at B = 128 (forward and input gradient; 256 -> 256 and 512 -> 256): average launch time over back-to-back
-launches incl. whatever epilogue launch the path needs.  VD_CONV_SM_OFF=1: the split-K kernels of rounds 2-5 (conv3_bx3_kernel + splitk_epilogue4);
-default: conv3_sm_kernel (whole K per workgroup).    python tools/conv_sm_probe.py"""
+launches on conv3_sm_kernel (whole K per workgroup).    python tools/conv_sm_probe.py"""
 import math
 import os
 import sys
@@ -58,4 +57,4 @@ for cin, cout, S in [(256, 256, 8), (512, 256, 8), (256, 256, 4), (512, 256, 4)]
             m = np.median(fs.reshape(-1, 8), axis=0)
             print(f"     {fs.shape[0]} workgroups, {stages} stages; cycles per stage: " + "  ".join(f"{SEG[k]} {m[k] / stages:6.0f}" for k in range(6))
                   + f"   epilogue {m[6]:6.0f}  loop total {m[7] - m[6]:7.0f} = {(m[7] - m[6]) / stages:6.0f} per stage")
-print(f"# sum {tot:.1f} us  (VD_CONV_SM_OFF={os.environ.get('VD_CONV_SM_OFF', '0')})")
+print(f"# sum {tot:.1f} us")

@@ -1,4 +1,4 @@
-"""A/B of the upsample-fused 3x3 convolution at 32x32 outputs (config #2: 256 -> 256 channels, B = 128): k32 kernel (VD_BX3_K32_UP32=1) vs the 128 x 512 tile."""
+"""Launch time of the upsample-fused 3x3 convolution at 32x32 / 16x16 outputs (config #2: 256 -> 256 channels, B = 128) on the kernel the planner picks."""
 import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -822,11 +822,10 @@ static bool gemm_bx3_eligible(const vd_gemm_desc& d) {
 // Split-K plan of the 128 x 128-tile 1x1 kernel (vd_gemm_tile 9): under three quarters of a round of tiles and at least four 64-channel
 // stages -> enough splits for ~two rounds, at least two stages each.  splits == 1: the direct epilogue.
 static void gemm_bx3_plan(const vd_gemm_desc& d, int& splits, int& st_per) {
-    static const int off = getenv("VD_GEMM_BX3_SPLIT_OFF") ? atoi(getenv("VD_GEMM_BX3_SPLIT_OFF")) : 0;
     const int base = vd_cdiv(d.M, 128) * (d.N / 128);
     const int nst = vd_cdiv(d.K / XC, GS);
     splits = 1, st_per = nst;
-    if (off || base >= 192 || nst < 4 || d.pool2 || d.act || d.gn_part) return;
+    if (base >= 192 || nst < 4 || d.pool2 || d.act || d.gn_part) return;
     splits = vd_cdiv(512, base);
     if (splits > nst / 2) splits = nst / 2;
     st_per = vd_cdiv(nst, splits);
@@ -844,8 +843,7 @@ static bool gemm_bx3_big_tile(const vd_gemm_desc& d) {
 static bool bx3_eligible(const vd_gemm_desc& d) {
     if (!d.a_packed || d.a_packed_mpad < d.M || (d.a_packed_mpad & 127) != 0) return false;
     if (d.b_mode == VD_B_CONV3_S2) {                              // stride 2 (round 3): 4x4 .. 32x32 outputs of an input twice as large
-        static const int s2_off = getenv("VD_BX3_S2_OFF") ? atoi(getenv("VD_BX3_S2_OFF")) : 0;
-        if (s2_off || d.d_trans || d.debug || d.tile || d.nb2 > 1 || d.gn_ss || d.pool2) return false;
+        if (d.d_trans || d.debug || d.tile || d.nb2 > 1 || d.gn_ss || d.pool2) return false;
         const bool wide2 = d.OW == 64 || (d.OW >= 128 && d.OW % 128 == 0);    // round 4: 64 / 128-pixel row-segment tiles (the 128x128 / 64x64 outputs of config #4)
         if ((d.OW != 4 && d.OW != 8 && d.OW != 16 && d.OW != 32 && !wide2) || d.OH != d.OW || d.H != 2 * d.OH || d.W != 2 * d.OW) return false;
         if (wide2 && ((d.OH * d.OW) % 128 != 0 || d.b_bstride >= (1ll << 29))) return false;
@@ -867,8 +865,7 @@ static bool bx3_eligible(const vd_gemm_desc& d) {
 // 8x8 layers: the channel loop is split over workgroups either way (too few tiles); with 128 x 256 tiles (four images, eight waves) every chunk of the
 // weight operand is fetched by half as many workgroups -- these layers re-read the weights once per pixel tile (64 tiles of 128 pixels at B = 128)
 static bool bx3_big_split(const vd_gemm_desc& d) {
-    static const int off = getenv("VD_BX3_BIGSPLIT_OFF") ? atoi(getenv("VD_BX3_BIGSPLIT_OFF")) : 0;
-    if (off || d.OW != 8 || d.OH != 8 || d.pool2 || d.gn_ss || d.N % 256 != 0) return false;
+    if (d.OW != 8 || d.OH != 8 || d.pool2 || d.gn_ss || d.N % 256 != 0) return false;
     if (d.b_mode != VD_B_CONV3 && d.b_mode != VD_B_CONV3_T) return false;
     const int base = vd_cdiv(d.M, 128) * (d.N / 256);
     return base >= 32 && base < 256 && d.C / XC >= 8;
@@ -901,11 +898,10 @@ static void bx3_plan(const vd_gemm_desc& d, int& splits, int& c_per) {
 // and the weight operand is fetched and stored once per 512 pixels)
 static int bx3_big_tile(const vd_gemm_desc& d, int splits) {
     if (splits != 1 || (d.OW != 16 && d.OW != 32) || d.N % 256 != 0) return 0;
-    static const int huge_off = getenv("VD_BX3_HUGE_OFF") ? atoi(getenv("VD_BX3_HUGE_OFF")) : 0;
     // ... for the FORWARD kinds (plain, upsample-fused, GroupNorm-folding loader): +8-11 % per kernel in isolation, 1.4 % of a sampler step, 0.6 % of a
     // training step.  Not for the flipped-tap input gradient: it runs beside the weight gradients of the side stream, and at 212 VGPRs and 87 KB of
     // LDS a 128 x 512 workgroup leaves no room on its CU for those workgroups, which is what fills the 128 x 256 kernels' bubbles (measured neutral).
-    if (!huge_off && d.b_mode != VD_B_CONV3_T && !d.pool2 && d.OW == 32 && d.N % 512 == 0) {
+    if (d.b_mode != VD_B_CONV3_T && !d.pool2 && d.OW == 32 && d.N % 512 == 0) {
         const int nh = vd_cdiv(d.M, 128) * (d.N / 512);
         if (nh >= 256 && (nh % 256 == 0 || nh % 256 >= 192)) return 2;
     }
@@ -913,11 +909,9 @@ static int bx3_big_tile(const vd_gemm_desc& d, int splits) {
     return (nb >= 256 && (nb % 256 == 0 || nb % 256 >= 192)) ? 1 : 0;
 }
 
-#include "vd_conv_k32.inc"
-
 // The persistent 16x16x32 kernel (vd_conv_k32p.hip) takes a stride-1 / upsample-fused convolution when its 256-pixel tiles fill the chip's 256
 // workgroup slots to >= 75 % in every round (a 128 x 256 tile per CU: 300 tiles would cost two rounds for 1.17 rounds of work; the 128 x 128
-// tiles below pack such grids two per CU).  VD_K32P_OFF=1: round 3's kernels.
+// tiles below pack such grids two per CU).
 static bool k32p_pick(const vd_gemm_desc& d) {
     if (d.b_mode != VD_B_CONV3 && d.b_mode != VD_B_CONV3_T && d.b_mode != VD_B_CONV3_UP) return false;
     if (!vd_conv3_k32p_eligible(d) || d.N % 256 != 0) return false;
@@ -926,17 +920,19 @@ static bool k32p_pick(const vd_gemm_desc& d) {
     return nt >= 192 && 4 * nt >= 3 * rounds * 256;
 }
 
-static int launch_bx3(const vd_gemm_desc& d, hipStream_t st) {
-    int splits, c_per;
-    bx3_plan(d, splits, c_per);
+// tile: vd_gemm_tile() of the problem -- 18 the persistent 16x16x32 kernel, 16 the 8x8 layers' 128 x 256 tiles with the channel loop split,
+// 15 / 12 the 128 x 512 / 128 x 256 tiles (eight waves, one workgroup per CU, unsplit), 8 the 128 x 128 tiles
+static int launch_bx3(const vd_gemm_desc& d, int tile, hipStream_t st) {
     const int mode = d.b_mode == VD_B_CONV3 ? (d.gn_ss ? 3 : 0) : (d.b_mode == VD_B_CONV3_T ? 1 : (d.b_mode == VD_B_CONV3_S2 ? 4 : 2));
-    if (!bx3_big_split(d) && k32p_pick(d)) {
+    if (tile == 18) {
         if (d.pool2 && (mode != 1 || d.bias || d.rowadd || d.residual || d.accumulate)) {
             vd_set_error("vd_gemm: pool2 needs VD_B_CONV3_T with a bare epilogue");
             return VD_EINVAL;
         }
         return vd_launch_conv3_k32p(d, mode, st) == 0 ? 0 : VD_EINVAL;
     }
+    int splits, c_per;
+    bx3_plan(d, splits, c_per);
     if (splits > 1 && d.ws == nullptr) {
         vd_set_error("vd_gemm: split-K workspace required (%d splits): query vd_gemm_ws_floats()", splits);
         return VD_EINVAL;
@@ -946,29 +942,17 @@ static int launch_bx3(const vd_gemm_desc& d, hipStream_t st) {
                      splits);
         return VD_EINVAL;
     }
-    bool done = false;
-    if (bx3_big_split(d)) {
+    if (tile == 16) {
         dim3 grids(vd_cdiv(d.M, 128) * (d.N / 256), splits);
         if (mode == 0) hipLaunchKernelGGL((conv3_bx3_kernel<8, 0, 2, 512, 2>), grids, dim3(512), 0, st, d, c_per);
         else hipLaunchKernelGGL((conv3_bx3_kernel<8, 1, 2, 512, 2>), grids, dim3(512), 0, st, d, c_per);
         if (splits > 1) launch_splitk_epilogue(d, splits, st);
         return 0;
     }
-    dim3 grid(vd_cdiv(d.M, 128) * vd_cdiv(d.N, 128), splits);
-    // 128 x 256 tiles (eight waves, one workgroup per CU) where whole rounds of 256 workgroups come out: the weight operand is then fetched
-    // from L2 and stored to LDS once per 256 pixels (measured 5-10 % faster at 16x16 / 32x32; a partly filled last round packs better
-    // with the 128 x 128 tiles, two per CU)
-    // 128 x 256 / 128 x 512 tiles (eight waves, one workgroup per CU) where whole rounds of 256 workgroups come out: the weight operand is then
-    // fetched from L2 and stored to LDS once per 256 / 512 pixels (measured +5-10 % each step at 16x16 / 32x32; a partly filled last round packs
-    // better with the 128 x 128 tiles, two per CU)
-    static const int big_off = getenv("VD_BX3_BIG_OFF") ? atoi(getenv("VD_BX3_BIG_OFF")) : 0;
-    const int big = (big_off || mode == 4) ? 0 : bx3_big_tile(d, splits);       // (stride 2: 128 x 128 tiles only)
-    // 16x16x32 MFMA, 32-channel K-steps, 128 x 256 tile (vd_conv_k32.inc): the chip holds a higher clock on that instruction shape
-    constexpr int keep_huge = 0;
-    // (the upsample-fused forward at 32x32 stays on the 128 x 512 tile: 348 us against 360-364 for the k32 kernel, profiles/r02 vs r03 sampler stats)
-    constexpr int k32_up32 = 0;
-    if (big >= 1 && !(big == 2 && (keep_huge || (mode == 2 && !k32_up32))) && conv3_k32_eligible(d) && launch_conv3_k32(d, mode, st)) return 0;
-    if (big == 2) {
+    // 128 x 256 / 128 x 512 tiles where whole rounds of 256 workgroups come out (bx3_big_tile): the weight operand is then fetched from L2 and
+    // stored to LDS once per 256 / 512 pixels (measured +5-10 % each step at 16x16 / 32x32; a partly filled last round packs better with the
+    // 128 x 128 tiles, two per CU)
+    if (tile == 15) {
         dim3 gridh(vd_cdiv(d.M, 128) * (d.N / 512), 1);
         switch (mode) {
         case 0: hipLaunchKernelGGL((conv3_bx3_kernel<32, 0, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
@@ -978,38 +962,40 @@ static int launch_bx3(const vd_gemm_desc& d, hipStream_t st) {
         }
         return 0;
     }
-    if (big == 1) {
+    bool done = false;
+    if (tile == 12) {
         dim3 gridb(vd_cdiv(d.M, 128) * (d.N / 256), 1);
-#define VD_BX3_BIG(WW, MD)                                                                                \
+#define BX3_BIG(WW, MD)                                                                                   \
     if (!done && d.OW == WW && mode == MD) {                                                              \
         hipLaunchKernelGGL((conv3_bx3_kernel<WW, MD, 2, 512, 2>), gridb, dim3(512), 0, st, d, c_per);      \
         done = true;                                                                                      \
     }
-        VD_BX3_BIG(32, 0) VD_BX3_BIG(32, 1) VD_BX3_BIG(32, 2) VD_BX3_BIG(32, 3)
-        VD_BX3_BIG(16, 0) VD_BX3_BIG(16, 1) VD_BX3_BIG(16, 2) VD_BX3_BIG(16, 3)
-#undef VD_BX3_BIG
-        if (done) return 0;
+        BX3_BIG(32, 0) BX3_BIG(32, 1) BX3_BIG(32, 2) BX3_BIG(32, 3)
+        BX3_BIG(16, 0) BX3_BIG(16, 1) BX3_BIG(16, 2) BX3_BIG(16, 3)
+#undef BX3_BIG
+        return done ? 0 : VD_EINVAL;
     }
-#define VD_BX3_CASE(WW, MD)                                                                   \
+    dim3 grid(vd_cdiv(d.M, 128) * vd_cdiv(d.N, 128), splits);
+#define BX3_CASE(WW, MD)                                                                      \
     if (!done && d.OW == WW && mode == MD) {                                                  \
         hipLaunchKernelGGL((conv3_bx3_kernel<WW, MD, 2>), grid, dim3(NT), 0, st, d, c_per);   \
         done = true;                                                                          \
     }
-    VD_BX3_CASE(32, 0) VD_BX3_CASE(32, 1) VD_BX3_CASE(32, 2) VD_BX3_CASE(32, 3)
-    VD_BX3_CASE(16, 0) VD_BX3_CASE(16, 1) VD_BX3_CASE(16, 2) VD_BX3_CASE(16, 3)
-    VD_BX3_CASE(8, 0) VD_BX3_CASE(8, 1) VD_BX3_CASE(8, 2)
-    VD_BX3_CASE(4, 0) VD_BX3_CASE(4, 1)
-    VD_BX3_CASE(32, 4) VD_BX3_CASE(16, 4) VD_BX3_CASE(8, 4) VD_BX3_CASE(4, 4)
-#define VD_BX3_WIDE(WW, MD)                                                                   \
+    BX3_CASE(32, 0) BX3_CASE(32, 1) BX3_CASE(32, 2) BX3_CASE(32, 3)
+    BX3_CASE(16, 0) BX3_CASE(16, 1) BX3_CASE(16, 2) BX3_CASE(16, 3)
+    BX3_CASE(8, 0) BX3_CASE(8, 1) BX3_CASE(8, 2)
+    BX3_CASE(4, 0) BX3_CASE(4, 1)
+    BX3_CASE(32, 4) BX3_CASE(16, 4) BX3_CASE(8, 4) BX3_CASE(4, 4)
+#define BX3_WIDE(WW, MD)                                                                      \
     if (!done && (WW == 64 ? d.OW == 64 : (d.OW >= 128 && d.OW % 128 == 0)) && mode == MD) {  \
         hipLaunchKernelGGL((conv3_bx3_kernel<WW, MD, 2>), grid, dim3(NT), 0, st, d, c_per);   \
         done = true;                                                                          \
     }
-    VD_BX3_WIDE(64, 0) VD_BX3_WIDE(64, 1) VD_BX3_WIDE(64, 2)
-    VD_BX3_WIDE(128, 0) VD_BX3_WIDE(128, 1) VD_BX3_WIDE(128, 2)
-    VD_BX3_WIDE(64, 4) VD_BX3_WIDE(128, 4)
-#undef VD_BX3_WIDE
-#undef VD_BX3_CASE
+    BX3_WIDE(64, 0) BX3_WIDE(64, 1) BX3_WIDE(64, 2)
+    BX3_WIDE(128, 0) BX3_WIDE(128, 1) BX3_WIDE(128, 2)
+    BX3_WIDE(64, 4) BX3_WIDE(128, 4)
+#undef BX3_WIDE
+#undef BX3_CASE
     if (!done) return VD_EINVAL;
     if (splits > 1) launch_splitk_epilogue(d, splits, st);
     return 0;

@@ -1,5 +1,5 @@
 // ---- split-precision 3x3 convolution on v_mfma_f32_16x16x32_bf16, PERSISTENT tile walk (round 4) ---------------------------------------
-// Same arithmetic, packed-weight layout, LDS images and MFMA loop as conv3_k32_kernel (vd_conv_k32.inc, round 3); what changes is everything
+// Same arithmetic, packed-weight layout, LDS images and MFMA loop as round 3's conv3_k32_kernel (retired); what changes is everything
 // AROUND the loop.  Round 3's kernel is one 128-channel x 256-pixel tile per workgroup, one workgroup per CU (143 KB of LDS): nothing on a CU
 // overlaps a tile's prologue (first weight stage + halo patch out of HBM, ~3 us) or its epilogue (128 KB of stores per workgroup, all 256
 // workgroups of a round at once: 33 MB, ~6 us of HBM writes with the matrix pipes idle).  Measured (profiles/r03_conv_k32_ab.txt, B = 128, 32x32,
@@ -670,10 +670,12 @@ __global__ __launch_bounds__(256) void pack_f16_multi_kernel(const int64_t* __re
         pack_f16_one<9>(reinterpret_cast<const float*>(jb[0]), reinterpret_cast<u32x4*>(jb[1]), M, C, (M + 127) / 128 * 128, jb[4], jb[5], local);
 }
 
+#ifdef VD_K32P_VARIANTS
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return v ? atoi(v) : dflt;
 }
+#endif
 
 }  // namespace
 
@@ -687,8 +689,7 @@ extern "C" int vd_conv3_pack_weights_f16_multi(const int64_t* table, int n_jobs,
 // What launch_bx3 (vd_gemm.hip) asks: can the persistent 16x16x32 kernel take this problem?  Output tiles of 256 pixels (16 x 16, or 8 rows x 32
 // columns of any image whose sides divide), whole chunk pairs, aligned float4 epilogue, and enough tiles to give every CU at least one.
 bool vd_conv3_k32p_eligible(const vd_gemm_desc& d) {
-    static const int off = env_int("VD_K32P_OFF", 0);
-    if (off || d.C % 32 != 0 || d.bias_on_n || d.d_trans || d.nb2 > 1) return false;
+    if (d.C % 32 != 0 || d.bias_on_n || d.d_trans || d.nb2 > 1) return false;
     if (d.b_presplit && (d.b_presplit != 1 || d.gn_ss || d.math == 2 || (d.b_bstride & 3) || (((uintptr_t)d.B) & 15))) return false;
     const int TW = d.OW == 16 ? 16 : 32, TR = 256 / TW;
     if (d.OW % TW != 0 || d.OH % TR != 0 || d.OH * d.OW != d.NP) return false;

@@ -307,17 +307,11 @@ __global__ __launch_bounds__(256, 2) void conv3_sm_kernel(const sm_args a) {
 #endif
 }
 
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 }  // namespace
 
 // vd_gemm.hip asks: is this one of the 8x8 / 4x4 stride-1 problems the whole-K kernel takes?  (vd_gemm_tile() == 20)
 bool vd_conv3_sm_eligible(const vd_gemm_desc& d) {
-    static const int off = env_int("VD_CONV_SM_OFF", 0);          // 1: rounds 2-5's split-K kernels (A/B switch)
-    if (off || !d.a_packed || d.math == 2 || d.b_presplit) return false;
+    if (!d.a_packed || d.math == 2 || d.b_presplit) return false;
     if (d.b_mode != VD_B_CONV3 && d.b_mode != VD_B_CONV3_T) return false;
     if (d.OH != d.OW || (d.OW != 8 && d.OW != 4) || d.H != d.OH || d.W != d.OW || d.OH * d.OW != d.NP) return false;
     if (d.C % 32 != 0 || d.K != d.C * 9 || d.M < 64 || d.a_packed_mpad < d.M || (d.a_packed_mpad & 127)) return false;

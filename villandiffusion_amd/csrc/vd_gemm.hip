@@ -1008,8 +1008,7 @@ static bool smallm_eligible(const vd_gemm_desc& d) {
 
 static int launch_smallm(const vd_gemm_desc& d, hipStream_t st) {
     const int nb = d.N / d.NP;
-    constexpr int fewout_off = 0;
-    if (!fewout_off && fewout_eligible(d)) {
+    if (fewout_eligible(d)) {
         const int64_t quads = (int64_t)nb * d.H * (d.W / 4);
         // eight waves per 256 pixels (round 6; four until then): 31 against 48 us for conv_out at B = 128 -- the loop is a latency chain (loads -> 100 FMAs per
         // channel) and four waves per workgroup left two per SIMD; sixteen: 34 us
@@ -2144,17 +2143,11 @@ extern "C" int vd_wg_stamps_set(void* buf) {          // diagnostic build only: 
 #endif
 
 extern "C" int64_t vd_gemm_ws_floats(const vd_gemm_desc* desc) {
-    if (desc && desc->a_packed && !bx3_eligible(*desc) && gemm_bx3_eligible(*desc) && desc->math != 2) {
-        if (vd_gemm_tile(desc) != 9) return 0;
-        int splits, st_per;
-        gemm_bx3_plan(*desc, splits, st_per);
-        return splits > 1 ? (int64_t)splits * desc->M * desc->N : 0;
-    }
-    if (desc && desc->a_packed) {
-        if (!bx3_eligible(*desc)) return 0;
-        if (vd_conv3_sm_eligible(*desc)) return 0;               // whole K per workgroup: no slabs
-        int splits, c_per;
-        bx3_plan(*desc, splits, c_per);
+    if (desc && desc->a_packed) {            // split-K slabs: the 1x1 kernel's tile 9 and the 3x3 kernel's tiles 8 / 16 (the others split nothing)
+        const int tile = vd_gemm_tile(desc);
+        int splits = 1, per;
+        if (tile == 9) gemm_bx3_plan(*desc, splits, per);
+        else if (tile == 8 || tile == 16) bx3_plan(*desc, splits, per);
         return splits > 1 ? (int64_t)splits * desc->M * desc->N : 0;
     }
     if (!desc || !patch_eligible(*desc)) return 0;
@@ -2182,25 +2175,19 @@ extern "C" int vd_gemm_tile(const vd_gemm_desc* desc) {
     }
     if (d.a_packed) {
         if (bx3_eligible(d)) {
-            int splits, c_per;
-            bx3_plan(d, splits, c_per);
-            static const int big_off = getenv("VD_BX3_BIG_OFF") ? atoi(getenv("VD_BX3_BIG_OFF")) : 0;
             if (vd_conv3_sm_eligible(d)) return 20;                    // 20: conv3_sm_kernel (8x8 / 4x4 levels: 64-channel x 2 | 4-image tiles, whole K, no split)
             if (bx3_big_split(d)) return 16;                           // 16: 8x8 layers, 128 x 256 tiles with the channel loop split
             if (k32p_pick(d)) return 18;                               // 18: conv3_k32p_kernel (persistent 16x16x32 kernel, any image of 8 x 32 segments)
-            const int big = (big_off || d.b_mode == VD_B_CONV3_S2) ? 0 : bx3_big_tile(d, splits);
-            constexpr int keep_huge = 0;
-            constexpr int k32_up32 = 0;
-            if (big >= 1 && !(big == 2 && (keep_huge || (d.b_mode == VD_B_CONV3_UP && !k32_up32))) && conv3_k32_eligible(d)) return 17;      // 17: conv3_k32_kernel (16x16x32 MFMA, 128 x 256 tile)
-            return big == 2 ? 15 : (big == 1 ? 12 : 8);                // 12 / 15: the 128 x 256 / 128 x 512 tile, eight waves
+            int splits, c_per;
+            bx3_plan(d, splits, c_per);
+            const int big = d.b_mode == VD_B_CONV3_S2 ? 0 : bx3_big_tile(d, splits);
+            return big == 2 ? 15 : (big == 1 ? 12 : 8);                // 12 / 15: the 128 x 256 / 128 x 512 tile, eight waves; 8: 128 x 128
         }
         if (!gemm_bx3_eligible(d)) return -1;
         if (vd_gemm1x1_k32p_pick(d)) return 19;                 // 19: gemm1x1_k32p_kernel (persistent 16x16x32 kernel, 128 x 256 tiles, LDS-DMA weights)
+        if (gemm_bx3_big_tile(d)) return 13;                    // 13: the 128 x 256 tile, eight waves
         // >= 2 tiles per resident workgroup (512 slots): the persistent variant walks them with the next tile's loads in flight
-        static const int gbig_off = getenv("VD_GEMM_BX3_BIG_OFF") ? atoi(getenv("VD_GEMM_BX3_BIG_OFF")) : 0;
-        if (!gbig_off && gemm_bx3_big_tile(d)) return 13;       // 13: the 128 x 256 tile, eight waves
-        constexpr int persist = 1;
-        return (persist && vd_cdiv(d.M, 128) * (d.N / 128) >= 1024) ? 11 : 9;
+        return vd_cdiv(d.M, 128) * (d.N / 128) >= 1024 ? 11 : 9;
     }
     if (d.math == 1) return gemm_bx3_act_eligible(d) ? 10 : -1;
     if (smallm_eligible(d)) return 7;                        // direct convolution for <= 4 output channels
@@ -2222,9 +2209,6 @@ extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
     vd_gemm_desc d = *desc;
     VD_REQUIRE(d.A && d.B && d.D, "vd_gemm: null operand");
     VD_REQUIRE(d.math != 3 || d.a_packed, "vd_gemm: math = 3 (one bf16 product per term) reads the hi plane of a_packed; a_packed is NULL");
-    VD_REQUIRE(d.b_presplit == 0 || (d.b_presplit == 1 && vd_gemm_tile(&d) == 18),
-               "vd_gemm: a pre-split B operand (b_presplit = %d) is read by the persistent 16x16x32 convolution only (vd_gemm_tile() == 18; this problem: %d)",
-               d.b_presplit, d.b_presplit == 1 ? vd_gemm_tile(&d) : 0);
 #ifndef VD_ABLATION
     VD_REQUIRE(d.debug == 0, "vd_gemm: desc.debug = %d -- timing-only ablation bits exist in `make ABLATION=1` builds only", d.debug);
 #endif
@@ -2241,8 +2225,6 @@ extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
             VD_REQUIRE(d.K == d.C * 9, "vd_gemm: conv K must be C*9");
     }
     VD_REQUIRE(d.act == 0 || (d.act == 1 && !d.a_packed && d.math == 0), "vd_gemm: act = 1 (ReLU) is honoured by the exact-f32 kernels only");
-    if (false) {
-    }
     if (d.a_bstride != 0) VD_REQUIRE(d.NP % 64 == 0, "vd_gemm: per-batch A needs NP %% 64 == 0 (NP=%d)", d.NP);
     VD_REQUIRE(!(d.d_trans && (d.residual || d.rowadd)), "vd_gemm: d_trans excludes residual/rowadd");
     if (d.nb2 > 1)
@@ -2253,12 +2235,15 @@ extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
                            "C %% 16 == 0, M >= 64, or a VD_B_PLAIN product with shared A, NP %% 128 == 0, K %% 16 == 0, M >= 64; "
                            "a_packed_mpad = M rounded up to 128; math = 1 needs per-batch A, PLAIN / KCONTIG B, NP %% 128 == 0, K %% 16 == 0, K >= 32, M >= 64; "
                            "math = 2 / 3 need the persistent 16x16x32 kernels (vd_gemm_tile 18 / 19; math = 3 also 20)");
-    VD_REQUIRE(!d.gn_ss || tile == 4 || tile == 6 || tile == 8 || tile == 12 || tile == 15 || tile == 17 || tile == 18,
+    VD_REQUIRE(d.b_presplit == 0 || (d.b_presplit == 1 && tile == 18),
+               "vd_gemm: a pre-split B operand (b_presplit = %d) is read by the persistent 16x16x32 convolution only (vd_gemm_tile() == 18; this problem: %d)",
+               d.b_presplit, tile);
+    VD_REQUIRE(!d.gn_ss || tile == 4 || tile == 6 || tile == 8 || tile == 12 || tile == 15 || tile == 18,
                "vd_gemm: gn_ss (GroupNorm folded into the loader) needs the patch-staged 3x3 kernel (OW 16/32, C %% 8 == 0, M >= 64)");
-    VD_REQUIRE(!d.pool2 || tile == 8 || tile == 12 || tile == 17 || tile == 18, "vd_gemm: pool2 needs the split-precision 3x3 kernel (VD_B_CONV3_T with a_packed)");
+    VD_REQUIRE(!d.pool2 || tile == 8 || tile == 12 || tile == 18, "vd_gemm: pool2 needs the split-precision 3x3 kernel (VD_B_CONV3_T with a_packed)");
     VD_REQUIRE(!d.act_out || (tile == 18 && d.gn_ss), "vd_gemm: act_out is written by the persistent 16x16x32 3x3 convolution with gn_ss only (vd_gemm_tile() == 18)");
-    VD_REQUIRE(!d.gn_part || ((tile == 17 || tile == 18) && !d.pool2),
-               "vd_gemm: gn_part is written by the 16x16x32 split-precision 3x3 kernels only (vd_gemm_tile() == 17 / 18)");
+    VD_REQUIRE(!d.gn_part || (tile == 18 && !d.pool2),
+               "vd_gemm: gn_part is written by the persistent 16x16x32 split-precision 3x3 kernel only (vd_gemm_tile() == 18)");
     hipStream_t st = (hipStream_t)stream;
     int rc;
     switch (tile) {
@@ -2268,7 +2253,7 @@ extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
         case 4:
         case 6: rc = launch_patch(d, st); break;
         case 7: rc = launch_smallm(d, st); break;
-        case 8: case 12: case 15: case 16: case 17: case 18: rc = launch_bx3(d, st); break;
+        case 8: case 12: case 15: case 16: case 18: rc = launch_bx3(d, tile, st); break;
         case 19: rc = vd_launch_gemm1x1_k32p(d, st) == 0 ? 0 : VD_EINVAL; break;
         case 20: rc = vd_launch_conv3_sm(d, st) == 0 ? 0 : VD_EINVAL; break;
         case 10: launch_gemm_bx3_act(d, st); rc = 0; break;
@@ -2405,13 +2390,10 @@ extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) {
             rc = 0;
             if (wgrad_patch_kind(d) == 4) {
                 const bool up = d.mode == VD_B_CONV3_UP;
-#define VD_WBX3(WW)                                                                                     \
+#define VD_WK32(WW)                                                                                     \
     do {                                                                                                \
-        if (wgrad_k32_enabled()) {                                                                      \
-            if (up) hipLaunchKernelGGL((wgrad_k32_kernel<WW, 2>), grid, dim3(NT), 0, st, d, kk_per);    \
-            else hipLaunchKernelGGL((wgrad_k32_kernel<WW, 0>), grid, dim3(NT), 0, st, d, kk_per);       \
-        } else if (up) hipLaunchKernelGGL((wgrad_bx3_kernel<WW, 2>), grid, dim3(NT), 0, st, d, kk_per); \
-        else hipLaunchKernelGGL((wgrad_bx3_kernel<WW, 0>), grid, dim3(NT), 0, st, d, kk_per);           \
+        if (up) hipLaunchKernelGGL((wgrad_k32_kernel<WW, 2>), grid, dim3(NT), 0, st, d, kk_per);        \
+        else hipLaunchKernelGGL((wgrad_k32_kernel<WW, 0>), grid, dim3(NT), 0, st, d, kk_per);           \
     } while (0)
                 if (d.mode == VD_B_CONV3_S2) {
                     if (d.OW >= 64) hipLaunchKernelGGL((wgrad_bx3_kernel<32, 4, true>), grid, dim3(NT), 0, st, d, kk_per);
@@ -2421,10 +2403,10 @@ extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) {
                 } else if (d.OW >= 64 && up) hipLaunchKernelGGL((wgrad_bx3_kernel<32, 2, true>), grid, dim3(NT), 0, st, d, kk_per);
                 else if (d.OW >= 64) hipLaunchKernelGGL((wgrad_bx3_kernel<32, 0, true>), grid, dim3(NT), 0, st, d, kk_per);
                 else if (d.OW == 4) hipLaunchKernelGGL((wgrad_bx3_kernel<4, 0>), grid, dim3(NT), 0, st, d, kk_per);
-                else if (d.OW == 32) VD_WBX3(32);
-                else if (d.OW == 16) VD_WBX3(16);
-                else VD_WBX3(8);
-#undef VD_WBX3
+                else if (d.OW == 32) VD_WK32(32);
+                else if (d.OW == 16) VD_WK32(16);
+                else VD_WK32(8);
+#undef VD_WK32
             } else if (wgrad_patch_kind(d) == 3) {
                 const int ohs = ilog2_exact(d.OH);
                 const bool up = d.mode == VD_B_CONV3_UP;
@@ -2543,14 +2525,13 @@ static int wgrad_group_class(const vd_wgrad_desc& d) {
 
 extern "C" int vd_conv_wgrad_group_class(const vd_wgrad_desc* desc) { return desc ? wgrad_group_class(*desc) : 0; }
 extern "C" int64_t vd_conv_wgrad_group_job_bytes(void) { return (int64_t)sizeof(vd_wgrad_job); }
-// Which kernel vd_conv_wgrad_group_launch runs for a class: 9 = wgrad9_group_kernel (all nine taps per workgroup), 32 = wgrad_k32_group_kernel
-// (16x16x32 one-tap-row kernel, the default where it applies), 0 = wgrad_bx3_group_kernel / wgrad1x1_bx3_group_kernel (profiling names, tests).
+// Which kernel vd_conv_wgrad_group_launch runs for a class: 32 = wgrad_k32_group_kernel (16x16x32 one-tap-row kernel), 256 =
+// wgrad1x1_wide_group_kernel, 3000 = wgrad_ps_group_kernel, 0 = wgrad_bx3_group_kernel (profiling names, tests).
 extern "C" int vd_conv_wgrad_group_variant(int cls) {
     if (cls > VD_WG_ONE) return vd_conv_wgrad_group_variant(cls - VD_WG_ONE);      // same kernel family, one product per term
     if (cls >= 3000) return 3000;                   // wgrad_ps_group_kernel (pre-split operands)
-    if (wgrad9_class(cls)) return 9;
-    if (cls == 1000) return wgrad1x1_wide_enabled() ? 256 : 0;
-    if (cls < 1000 && cls != 4 * 4 + 0 && !(cls & 1) && wgrad_k32_enabled()) return 32;
+    if (cls == 1000) return 256;
+    if (cls < 1000 && cls != 4 * 4 + 0 && !(cls & 1)) return 32;
     return 0;
 }
 
@@ -2563,16 +2544,12 @@ extern "C" int vd_conv_wgrad_group_plan(const vd_wgrad_desc* descs, int n, void*
     VD_REQUIRE(cls != 0, "vd_conv_wgrad_group_plan: job 0 is not a groupable split-precision (math = 1) or one-product (math = 3) 3x3 / 1x1 weight gradient");
     vd_wgrad_job* jobs = reinterpret_cast<vd_wgrad_job*>(table_out);
     const int bcls = cls > VD_WG_ONE ? cls - VD_WG_ONE : cls;     // the geometry (tiles, K-steps, targets) of a math = 3 class is its math = 1 class's
-    const bool one = bcls == 1000;
-    const bool nine = bcls < 3000 && wgrad9_class(bcls);           // one workgroup (512 threads, one per CU) per tile produces all nine taps
-    const bool wide1 = one && wgrad1x1_wide_enabled();           // 1x1: BM x 256 tiles, 32-pixel K-steps, one 512-thread workgroup per CU
+    const bool one = bcls == 1000;                 // 1x1: BM x 256 tiles, 32-pixel K-steps, one 512-thread workgroup per CU
     auto job_base = [&](const vd_wgrad_desc& d) -> int64_t {
-        if (wide1) return (int64_t)vd_cdiv(d.M, wgrad1x1_wide_bm(d)) * vd_cdiv(d.C, 256);
-        return one ? (int64_t)vd_cdiv(d.M, 128) * vd_cdiv(d.C, 128) : (int64_t)vd_cdiv(d.M, 128) * vd_cdiv(d.C, 64) * (nine ? 1 : 3);
+        return one ? (int64_t)vd_cdiv(d.M, wgrad1x1_wide_bm(d)) * vd_cdiv(d.C, 256) : (int64_t)vd_cdiv(d.M, 128) * vd_cdiv(d.C, 64) * 3;
     };
     auto job_ks = [&](const vd_wgrad_desc& d) -> int64_t {
-        if (wide1) return ((int64_t)d.nb * (d.NP >> 3) + 3) >> 2;
-        return one ? (((int64_t)d.nb * (d.NP >> 3) + 7) >> 3) : (((int64_t)d.nb * d.NP + 31) / 32);
+        return one ? (((int64_t)d.nb * (d.NP >> 3) + 3) >> 2) : (((int64_t)d.nb * d.NP + 31) / 32);
     };
     int64_t work = 0;
     for (int j = 0; j < n; ++j) {
@@ -2587,21 +2564,17 @@ extern "C" int vd_conv_wgrad_group_plan(const vd_wgrad_desc* descs, int n, void*
     // 1.93 -> 1.46 ms and at 16x16 1.71 -> 1.29 ms going from ~650 to 128 steps (32 pixels each) per workgroup; 1x1 (64-pixel steps) 1.0 -> 0.76 ms
     // at 32 steps; still shorter ranges (more slabs) lose again.
     static const int t3 = getenv("VD_WGRAD_GROUP_TARGET") ? atoi(getenv("VD_WGRAD_GROUP_TARGET")) : 768;
-    static const int t1 = getenv("VD_W1X1_GROUP_TARGET") ? atoi(getenv("VD_W1X1_GROUP_TARGET")) : 512;
     static const int cap3 = getenv("VD_WGRAD_GROUP_KCAP") ? atoi(getenv("VD_WGRAD_GROUP_KCAP")) : 128;
-    static const int cap1 = getenv("VD_W1X1_GROUP_KCAP") ? atoi(getenv("VD_W1X1_GROUP_KCAP")) : 32;
-    static const int t9 = getenv("VD_WGRAD9_TARGET") ? atoi(getenv("VD_WGRAD9_TARGET")) : 256;
-    static const int cap9 = getenv("VD_WGRAD9_KCAP") ? atoi(getenv("VD_WGRAD9_KCAP")) : 128;
     static const int tw = getenv("VD_W1X1_WIDE_TARGET") ? atoi(getenv("VD_W1X1_WIDE_TARGET")) : 256;
     static const int capw = getenv("VD_W1X1_WIDE_KCAP") ? atoi(getenv("VD_W1X1_WIDE_KCAP")) : 64;
-    const bool k32 = bcls >= 3000 || (!one && !nine && bcls != 4 * 4 + 0 && !(bcls & 1) && wgrad_k32_enabled());      // two workgroups per CU: 512 resident slots
+    const bool k32 = bcls >= 3000 || (!one && bcls != 4 * 4 + 0 && !(bcls & 1));      // two workgroups per CU: 512 resident slots
     // (512 = the resident slots; 448 / 384 measured 0.15 ms per config-#2 step faster, same box, three interleaved rounds: the small classes get
     // longer K ranges and fewer slabs, the large ones are capped at 128 steps either way -- profiles/r04_wgrad_k32_target.txt)
     static const int t32 = getenv("VD_WGRAD_K32_TARGET") ? atoi(getenv("VD_WGRAD_K32_TARGET")) : 448;
-    const int target = wide1 ? tw : (one ? t1 : (nine ? t9 : (k32 ? t32 : t3)));
-    const int min_ks = one ? (wide1 ? 8 : 4) : 8;
+    const int target = one ? tw : (k32 ? t32 : t3);
+    constexpr int min_ks = 8;
     int64_t per = (work + target - 1) / target;                  // K-steps per workgroup
-    const int cap = wide1 ? capw : (one ? cap1 : (nine ? cap9 : cap3));
+    const int cap = one ? capw : cap3;
     if (per > cap) per = cap;
     // (A round-quantised choice of the K-range length measured neutral and is gone: profiles/HISTORY.md "VD_WGRAD_QUANT".)
     if (per < min_ks) per = min_ks;
@@ -2662,7 +2635,6 @@ extern "C" int vd_conv_wgrad_group_launch(const void* dev_table, int n, int cls,
     const dim3 grid(blocks);
     switch (cls) {
         case VD_WG_ONE + 1000: {
-            VD_REQUIRE(wgrad1x1_wide_enabled(), "vd_conv_wgrad_group_launch: class %d needs the wide 1x1 kernel (VD_W1X1_WIDE)", cls);
             static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<true>),
                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
             VD_REQUIRE(attr1 == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
@@ -2671,7 +2643,6 @@ extern "C" int vd_conv_wgrad_group_launch(const void* dev_table, int n, int cls,
         }
         case VD_WG_ONE + 4 * 32 + 0: case VD_WG_ONE + 4 * 32 + 2: case VD_WG_ONE + 4 * 16 + 0: case VD_WG_ONE + 4 * 16 + 2:
         case VD_WG_ONE + 4 * 8 + 0: case VD_WG_ONE + 4 * 8 + 2: {
-            VD_REQUIRE(vd_conv_wgrad_group_variant(cls) == 32, "vd_conv_wgrad_group_launch: class %d needs the 16x16x32 kernel (VD_WGRAD_K32)", cls);
             const int wc = (cls - VD_WG_ONE) / 4;
             const bool up = (cls - VD_WG_ONE) & 2;
             if (wc == 32) {
@@ -2691,34 +2662,21 @@ extern "C" int vd_conv_wgrad_group_launch(const void* dev_table, int n, int cls,
             VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - VD_WG_ONE - 3000) / 4, (cls - VD_WG_ONE - 3000) & 2, blocks, st, true) == 0,
                        "vd_conv_wgrad_group_launch: no pre-split kernel for class %d", cls);
             break;
-        case 1000:
-            if (wgrad1x1_wide_enabled()) {
-                static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<>),
-                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
-                VD_REQUIRE(attr == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
-                hipLaunchKernelGGL(wgrad1x1_wide_group_kernel<>, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
-            } else {
-                hipLaunchKernelGGL(wgrad1x1_bx3_group_kernel, grid, dim3(NT), 0, st, jobs, n);
-            }
+        case 1000: {
+            static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<>),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
+            VD_REQUIRE(attr == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
+            hipLaunchKernelGGL(wgrad1x1_wide_group_kernel<>, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
             break;
-#define VD_WG_K32(WW, MD)                                                                                   \
-    if (wgrad_k32_enabled()) hipLaunchKernelGGL((wgrad_k32_group_kernel<WW, MD>), grid, dim3(NT), 0, st, jobs, n); \
-    else hipLaunchKernelGGL((wgrad_bx3_group_kernel<WW, MD>), grid, dim3(NT), 0, st, jobs, n);
-        case 4 * 32 + 0:
-            if (wgrad9_class(cls)) hipLaunchKernelGGL((wgrad9_group_kernel<32>), grid, dim3(512), 0, st, jobs, n, wgrad9_flags());
-            else { VD_WG_K32(32, 0) }
-            break;
-        case 4 * 32 + 2: VD_WG_K32(32, 2) break;
+        }
+        case 4 * 32 + 0: hipLaunchKernelGGL((wgrad_k32_group_kernel<32, 0>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 32 + 2: hipLaunchKernelGGL((wgrad_k32_group_kernel<32, 2>), grid, dim3(NT), 0, st, jobs, n); break;
         case 4 * 32 + 1: hipLaunchKernelGGL((wgrad_bx3_group_kernel<32, 0, true>), grid, dim3(NT), 0, st, jobs, n); break;
         case 4 * 32 + 3: hipLaunchKernelGGL((wgrad_bx3_group_kernel<32, 2, true>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 16 + 0:
-            if (wgrad9_class(cls)) hipLaunchKernelGGL((wgrad9_group_kernel<16>), grid, dim3(512), 0, st, jobs, n, wgrad9_flags());
-            else { VD_WG_K32(16, 0) }
-            break;
-        case 4 * 16 + 2: VD_WG_K32(16, 2) break;
-        case 4 * 8 + 0: VD_WG_K32(8, 0) break;
-        case 4 * 8 + 2: VD_WG_K32(8, 2) break;
-#undef VD_WG_K32
+        case 4 * 16 + 0: hipLaunchKernelGGL((wgrad_k32_group_kernel<16, 0>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 16 + 2: hipLaunchKernelGGL((wgrad_k32_group_kernel<16, 2>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 8 + 0: hipLaunchKernelGGL((wgrad_k32_group_kernel<8, 0>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 8 + 2: hipLaunchKernelGGL((wgrad_k32_group_kernel<8, 2>), grid, dim3(NT), 0, st, jobs, n); break;
         case 4 * 4 + 0: hipLaunchKernelGGL((wgrad_bx3_group_kernel<4, 0>), grid, dim3(NT), 0, st, jobs, n); break;
         case 3000 + 4 * 32: case 3000 + 4 * 16: case 3000 + 4 * 8: case 3000 + 4 * 32 + 2: case 3000 + 4 * 16 + 2: case 3000 + 4 * 8 + 2:
             VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - 3000) / 4, (cls - 3000) & 2, blocks, st, false) == 0,

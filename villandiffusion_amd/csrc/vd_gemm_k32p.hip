@@ -355,17 +355,18 @@ __global__ __launch_bounds__(512, 2) void gemm1x1_k32p_kernel(const g32p_args a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the unused loads of the last two stages
 }
 
+#ifdef VD_G32P_VARIANTS
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return v ? atoi(v) : dflt;
 }
+#endif
 
 }  // namespace
 
 // vd_gemm.hip asks: can the persistent 16x16x32 1x1 kernel take this VD_B_PLAIN / a_packed problem, and is its grid worth it?
 bool vd_gemm1x1_k32p_pick(const vd_gemm_desc& d) {
-    static const int off = env_int("VD_G32P_OFF", 0);
-    if (off || !d.a_packed || d.b_mode != VD_B_PLAIN) return false;
+    if (!d.a_packed || d.b_mode != VD_B_PLAIN) return false;
     if (d.K % 64 != 0 || d.N % 256 != 0 || d.NP % 4 != 0 || d.M < 64 || d.a_packed_mpad < d.M || (d.a_packed_mpad & 127)) return false;
     if (d.bias_on_n || d.d_trans || d.nb2 > 1 || d.a_bstride != 0 || d.rowadd || d.gn_ss || d.gn_part || d.debug || d.tile || d.act || d.pool2) return false;
     if ((d.ldd & 3) || (d.d_bstride & 3) || (((uintptr_t)d.D) & 15) || (((uintptr_t)d.a_packed) & 15)) return false;
@@ -377,7 +378,7 @@ bool vd_gemm1x1_k32p_pick(const vd_gemm_desc& d) {
     const int rounds = vd_cdiv(nt, 256);
     constexpr int min_tiles = 192;          // (lower thresholds measured neutral: profiles/r04_g32p_min_tiles.txt)
     if (nt < min_tiles) return false;
-    return nt < 192 || 4 * nt >= 3 * rounds * 256;                // every round of 256 workgroup slots at least 75 % full
+    return 4 * nt >= 3 * rounds * 256;                // every round of 256 workgroup slots at least 75 % full
 }
 
 int vd_launch_gemm1x1_k32p(const vd_gemm_desc& d, hipStream_t st) {
@@ -390,8 +391,7 @@ int vd_launch_gemm1x1_k32p(const vd_gemm_desc& d, hipStream_t st) {
         n_cu &= ~7;
         if (n_cu < 8) n_cu = 8;
     }
-    static const int bm256 = env_int("VD_G32P_BM256", 1);         // A/B switch: 0 = the 128 x 256 tile everywhere (round 4)
-    const bool big_m = bm256 && d.math != 2 && d.M % 256 == 0 && d.N % 128 == 0;
+    const bool big_m = d.math != 2 && d.M % 256 == 0 && d.N % 128 == 0;
     g32p_args a;
 #ifdef VD_G32P_VARIANTS
     a.flags = env_int("VD_G32P_FLAGS", 0);

@@ -1,7 +1,7 @@
 // ---- split-precision weight gradient of a 1x1 convolution on WIDE tiles (round 3) ---------------------------------------------
 // Included by vd_wgrad_bx3.inc after wgrad1x1_bx3_body (same namespace, same plain [z][M][C] slabs, same job table and reduce grid).
 //
-// wgrad1x1_bx3_group_kernel is the one HBM-bound MFMA kernel of the training step: 6.6 TB/s of FETCH + WRITE traffic, 2.28 x its
+// The grouped 1x1 launch on wgrad1x1_bx3_body's 128 x 128 tiles (retired) was the one HBM-bound MFMA kernel of the training step: 6.6 TB/s of FETCH + WRITE traffic, 2.28 x its
 // algorithmic bytes (profiles/r02_pmc_traffic.json, r03_pmc_traffic.json) -- a 128 x 128 tile re-reads the dY rows once per 128 channels of
 // X and the X rows once per 128 rows of dY, and K (the pixels) is so long that every re-read comes from beyond L2.  A BM x 256 tile
 // (BM = 256 when the layer has more than 128 output channels, else 128) loads (BM + 256) rows per BM x 256 outputs: 0.50 x (256 x 256) or
@@ -173,8 +173,4 @@ __global__ __launch_bounds__(512, 2) void wgrad1x1_wide_group_kernel(const vd_wg
 
 constexpr int W1X1_WIDE_LDS = 2 * (2 * 4 * (256 + 2) + 2 * 4 * (256 + 2)) * 16;      // 132 096 B (BM = 256)
 
-static bool wgrad1x1_wide_enabled() {
-    static const int on = getenv("VD_W1X1_WIDE") ? atoi(getenv("VD_W1X1_WIDE")) : 1;
-    return on != 0;
-}
 static inline int wgrad1x1_wide_bm(const vd_wgrad_desc& d) { return d.M > 128 ? 256 : 128; }

@@ -344,7 +344,6 @@ __global__ __launch_bounds__(NT, 3) void wgrad_bx3_group_kernel(const vd_wgrad_j
 }
 
 #include "vd_wgrad_k32.inc"
-#include "vd_wgrad9.inc"
 
 // ---- split-precision weight gradient of a 1x1 convolution:  dW[m][c] = sum_{b,p} dY[b][m][p] * X[b][c][p]  ------------------
 // Both operands are pixel-contiguous, so a lane's 8-deep k-fragment is one aligned 32-byte read of each.  A workgroup owns a
@@ -480,14 +479,6 @@ __device__ __forceinline__ void wgrad1x1_bx3_body(const vd_wgrad_desc& d, int ks
 
 __global__ __launch_bounds__(NT, 2) void wgrad1x1_bx3_kernel(const vd_wgrad_desc d, int ksteps_per_split) {
     wgrad1x1_bx3_body(d, ksteps_per_split, gridDim.x, gridDim.y, blockIdx.x + gridDim.x * blockIdx.y);
-}
-
-__global__ __launch_bounds__(NT, 2) void wgrad1x1_bx3_group_kernel(const vd_wgrad_job* __restrict__ jobs, int n_jobs) {
-    const vd_wgrad_job* __restrict__ jb = jobs + wgrad_find_job(jobs, n_jobs, blockIdx.x, false);
-    const int lin = blockIdx.x - jb->first_block;
-    if (lin >= jb->gx * jb->gy) return;
-    const vd_wgrad_desc d = jb->d;
-    wgrad1x1_bx3_body(d, jb->ks_per, jb->gx, jb->gy, lin);
 }
 
 #include "vd_wgrad1x1_wide.inc"

@@ -4,7 +4,7 @@
 //
 // What changes against wgrad_bx3_body (8x8 / 16x16 / 32x32 outputs, plain and upsample-fused):
 //  * One MFMA contracts the whole K-step: 32 pixels = the four pixel octets of the step, k-group g = lane >> 4 = octet g.
-//    (The chip holds a higher clock on this instruction shape: see vd_conv_k32.inc.)
+//    (The chip holds a higher clock on this instruction shape.)
 //  * X is written to LDS ONCE, not three times.  The old kernel stored three copies of the X tile shifted by the horizontal tap (24 of
 //    its 40 KB of LDS stores per K-step, and 12 of its 20 fragment reads per wave); at three workgroups per CU those stores kept the LDS
 //    busier than the MFMAs kept the matrix pipe.  Here a lane reads the aligned octet of its channel and builds the two shifted fragments
@@ -290,11 +290,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_k32_group_kernel(const vd_wgrad_j
 // Round 3 (one register set, loads one step ahead): 0.93-0.97 x of wgrad_bx3_body on seven of the eight layer shapes of config #2 -- the halved LDS
 // traffic and the single barrier did not pay for dropping from three workgroups per CU to two.  Round 4 (two register sets, loads two steps ahead,
 // every load unconditional so that the stores wait with vmcnt(6), 234 VGPRs): 1.02 x (1.45 / 1.23 ms against 1.48 / 1.26 for the grouped 32x32 /
-// 16x16 launches, training step -0.5 % on three same-box pairs) -- the default for the classes it takes since then (VD_WGRAD_K32=0: the three-copy
-// kernel).  In-kernel stamps (profiles/r04_wgrad_stamps.txt): both kernels sit on the same ~1.4 ms for config #2's ten 32x32 layers at a matrix-pipe
+// 16x16 launches, training step -0.5 % on three same-box pairs) -- the only kernel of the classes it takes since then (the three-copy kernel's
+// instantiations for them are retired).  In-kernel stamps (profiles/r04_wgrad_stamps.txt): both kernels sit on the same ~1.4 ms for config #2's ten 32x32 layers at a matrix-pipe
 // utilisation of 64 % (1.9 GHz) vs 73 % (1.65 GHz) -- util x clock is the invariant, i.e. the launch is power-limited; static priorities that put
 // the two workgroups of a CU in anti-phase and re-ordered MFMA dependency chains moved single workgroups but not the launch.
-static bool wgrad_k32_enabled() {
-    static const int on = getenv("VD_WGRAD_K32") ? atoi(getenv("VD_WGRAD_K32")) : 1;
-    return on != 0;
-}

@@ -243,10 +243,9 @@ def _gemm_ws(n_floats: int, device):
 def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bstride=0, ldb=0, b_bstride=0,
          ldd=0, d_bstride=0, bias=None, bias_on_n=False, rowadd=None, rowadd_bstride=0, residual=None,
          res_bstride=0, conv=None, alpha=1.0, d_trans=False, accumulate=False, tile=0, debug=0, pad=0, nb2=0, a_b2stride=0,
-         b_b2stride=0, d_b2stride=0, gn_ss=None, a_packed=None, math_mode=0, pool2=False, convg=None, act=0, gn_part=None, act_out=None,
-         b_presplit=False):
+         b_b2stride=0, d_b2stride=0, gn_ss=None, a_packed=None, math_mode=0, pool2=False, convg=None, act=0, gn_part=None, b_presplit=False):
     """gn_part: optional [B, NP // 256, M, 2] buffer for the per-tile channel sums of the result (vd_gemm_desc.gn_part); it is filled only when the
-    launch goes to the 16x16x32 split-precision convolution -- ops.GN_PART_WRITTEN tells the caller right after the call."""
+    launch goes to the persistent 16x16x32 split-precision convolution -- ops.GN_PART_WRITTEN tells the caller right after the call."""
     global GN_PART_WRITTEN
     d = GemmDesc()
     d.act = act
@@ -291,17 +290,7 @@ def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bs
             d.a_packed, d.math = a_packed.data_ptr(), math_mode
     LAST_GEMM_MATH = d.math
     LAST_GEMM_TILE = lib.vd_gemm_tile(C.byref(d))            # kernel family the library picks for this problem (tests assert on it)
-    global ACT_OUT_WRITTEN
-    ACT_OUT_WRITTEN = False
-    if act_out is not None and gn_ss is not None and (a_packed16 is None or alt_math == 3):
-        # side output of the persistent kernel's GroupNorm-folding loader (vd_gemm_desc.act_out): taken only where that kernel runs the problem
-        d.act_out, d.act_bstride = act_out.data_ptr(), _img(act_out)[4]
-        if lib.vd_gemm_tile(C.byref(d)) == 18:
-            ACT_OUT_WRITTEN = True
-        else:
-            d.act_out, d.act_bstride = None, 0
-        LAST_GEMM_TILE = lib.vd_gemm_tile(C.byref(d))
-    GN_PART_WRITTEN = gn_part is not None and not pool2 and LAST_GEMM_TILE in (17, 18)
+    GN_PART_WRITTEN = gn_part is not None and not pool2 and LAST_GEMM_TILE == 18
     if GN_PART_WRITTEN:
         assert gn_part.is_contiguous() and gn_part.numel() >= (N // 256) * M * 2
         d.gn_part = gn_part.data_ptr()
@@ -328,14 +317,11 @@ def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bs
         name = f"gemm_bx3_act_kernel<{int(a_mode == A_ROW)}, {int(b_mode == B_KCONTIG)}>"
     elif tl == 19:
         # (the 256 x 128 tile where M % 256 == 0: vd_launch_gemm1x1_k32p; symbol names as rocprofv3 prints them)
-        big = d.math != 2 and M % 256 == 0 and N % 128 == 0 and os.environ.get("VD_G32P_BM256", "1") != "0"
+        big = d.math != 2 and M % 256 == 0 and N % 128 == 0
         name = ("gemm1x1_k32p_kernel<true, 128>" if d.math == 2 else
                 f"gemm1x1_k32p_kernel<false, {256 if big else 128}{', true' if d.math == 3 else ''}>")
     elif tl in (9, 11, 13):
         name = "gemm_bx3_persist_kernel" if tl == 11 else f"gemm_bx3_kernel<{512 if tl == 13 else 256}>"
-    elif tl == 17:
-        md = (3 if gn_ss is not None else 0) if b_mode == B_CONV3 else (1 if b_mode == B_CONV3_T else 2)
-        name = f"conv3_k32_kernel<{d.OW}, {md}>"
     elif tl == 18:          # the persistent kernel: template width 16 (16x16 images) or 32 (8-row x 32-column segments of any image); image width beside it
         md = (3 if gn_ss is not None else 0) if b_mode == B_CONV3 else (1 if b_mode == B_CONV3_T else 2)
         name = (f"conv3_k32p_kernel<{16 if d.OW == 16 else 32}, {md}, true, true, {'true' if d.math == 2 else 'false'}, {'true' if d.b_presplit else 'false'}"
@@ -415,8 +401,7 @@ WEIGHTS_EPOCH = 0
 def bx3_eligible(M, Cc, OH, OW, mode) -> bool:
     """Problems the split-precision convolution kernel takes (vd_gemm_desc.a_packed)."""
     if mode == B_CONV3_S2:                                  # stride 2 (OH, OW: the OUTPUT, half the input): square 4x4 .. 32x32 outputs, 64 / 128 k wide ones
-        return Cc % 16 == 0 and M >= 64 and OH == OW and (OW in (4, 8, 16, 32, 64) or (OW >= 128 and OW % 128 == 0)) \
-            and os.environ.get("VD_BX3_S2_OFF", "0") in ("", "0")
+        return Cc % 16 == 0 and M >= 64 and OH == OW and (OW in (4, 8, 16, 32, 64) or (OW >= 128 and OW % 128 == 0))
     if mode not in (B_CONV3, B_CONV3_T, B_CONV3_UP) or Cc % 16 != 0 or M < 64 or (OW == 4 and mode == B_CONV3_UP):
         return False
     if OW == 64 or (OW >= 128 and OW % 128 == 0):           # row-segment tiles of wide images
@@ -431,14 +416,13 @@ def bx3_pool2_eligible(M, Cc, OH, OW, nb) -> bool:
 
 
 GN_PART_WRITTEN = False
-ACT_OUT_WRITTEN = False
 LAST_GEMM_TILE = 0
 LAST_GEMM_MATH = 0
 FORCE_WS = None
 
 
 def conv3x3(x, w2d, bias, out, mode=B_CONV3, rowadd=None, rowadd_bstride=0, residual=None, accumulate=False, tile=0, debug=0,
-            pad=0, gn_ss=None, a_packed=None, pool2=False, gn_part=None, act_out=None):
+            pad=0, gn_ss=None, a_packed=None, pool2=False, gn_part=None):
     """out[b] = W (*) gather_mode(x[b]) + bias (+ rowadd[b,:,None,None]) (+ residual).  w2d: [M, C*9].
     pad: stride-2 mode only (0: zero pad (0,1,0,1); 1: symmetric padding 1).
     pool2 (B_CONV3_T with a_packed only): `out` has HALF the resolution and receives the 2x2 block sums of the result."""
@@ -460,7 +444,7 @@ def conv3x3(x, w2d, bias, out, mode=B_CONV3, rowadd=None, rowadd_bstride=0, resi
     return gemm(w2d, x, out, M=M, N=Bn * OH * OW, K=Cc * 9, b_mode=mode, NP=OH * OW, lda=Cc * 9, b_bstride=xbs,
                 ldd=OHo * OWo, d_bstride=obs, bias=bias, rowadd=rowadd, rowadd_bstride=rowadd_bstride,
                 residual=residual, res_bstride=rbs, conv=(Cc, H, W, OH, OW), accumulate=accumulate, tile=tile, debug=debug,
-                pad=pad, gn_ss=gn_ss, a_packed=a_packed, pool2=pool2, gn_part=gn_part, act_out=act_out, b_presplit=ps)
+                pad=pad, gn_ss=gn_ss, a_packed=a_packed, pool2=pool2, gn_part=gn_part, b_presplit=ps)
 
 
 def conv2d_general(x, w2d, bias, out, kh, kw, stride=1, pad_h=0, pad_w=0, relu=False):
@@ -720,9 +704,7 @@ def conv_wgrad_group(descs: Sequence[WgradDesc], device):
     elif ent["cls"] > 2000:                                      # stride-2 3x3 classes (2000 + output width; 2033: 32-pixel segments of wide outputs)
         name = "wgrad_bx3_group_kernel<32, 4, true>(+group_reduce)" if ent["cls"] == 2033 else f"wgrad_bx3_group_kernel<{ent['cls'] - 2000}, 4, false>(+group_reduce)"
     elif ent["cls"] == 1000:                                     # symbol names as rocprofv3 prints them
-        name = "wgrad1x1_wide_group_kernel(+group_reduce)" if var == 256 else "wgrad1x1_bx3_group_kernel(+group_reduce)"
-    elif var == 9:
-        name = f"wgrad9_group_kernel<{ent['cls'] // 4}>(+group_reduce)"
+        name = "wgrad1x1_wide_group_kernel(+group_reduce)"
     elif var == 32:
         name = f"wgrad_k32_group_kernel<{ent['cls'] // 4}, {ent['cls'] & 2}>(+group_reduce)"
     else:

@@ -189,13 +189,13 @@ class _Conv:
     def w2d(self):
         return self.net.P[self.prefix + ".weight"].view(self.cout, self.cin * 9)
 
-    def fwd(self, x, out, rowadd=None, rowadd_bstride=0, residual=None, gn_ss=None, gn_part=None, act_out=None):
+    def fwd(self, x, out, rowadd=None, rowadd_bstride=0, residual=None, gn_ss=None, gn_part=None):
         """gn_part: buffer for the per-tile channel sums of `out` (ops.conv3x3); ops.GN_PART_WRITTEN says whether this launch filled it."""
         pk = _bx3_packed(self.net, self.prefix, False, self.cout, self.cin, out.shape[2], out.shape[3], self.mode)
         if gn_ss is not None and (out.shape[3] not in (16, 32) or self.mode != B_CONV3):
             pk = None                                      # the folded-GroupNorm loader of the split-precision kernel: 16x16 / 32x32 only
         return ops.conv3x3(x, self.w2d(), self.net.P[self.prefix + ".bias"], out, mode=self.mode, rowadd=rowadd,
-                           rowadd_bstride=rowadd_bstride, residual=residual, pad=self.pad, gn_ss=gn_ss, a_packed=pk, gn_part=gn_part, act_out=act_out)
+                           rowadd_bstride=rowadd_bstride, residual=residual, pad=self.pad, gn_ss=gn_ss, a_packed=pk, gn_part=gn_part)
 
     def us_input(self, h, save):
         """Upsample2D's convolution (round 6): its input -- a block output, f32 -- as a pre-split image when the persistent kernel reads one for this shape.
@@ -293,32 +293,17 @@ class _Norm:
     def ps_ok(self, HW: int) -> bool:
         return ops.groupnorm_presplit_ok(self.ch, HW, self.groups)
 
-    def stats(self, x, full=False):
-        """Statistics-only pass: [B, C, 2] scale / shift pairs consumed by _Conv.fwd(gn_ss=...) (inference path; round 4: the training forward
-        too).  full: also the (mean, rstd) the backward pass needs."""
+    def stats(self, x):
+        """Statistics-only pass: [B, C, 2] scale / shift pairs consumed by _Conv.fwd(gn_ss=...) (inference path)."""
         net = self.net
         B = x.shape[0]
         ss = torch.empty((B, self.ch, 2), device=x.device, dtype=torch.float32)
         mean = torch.empty(B * self.groups, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         ops.groupnorm_stats(x, net.P[self.prefix + ".weight"], net.P[self.prefix + ".bias"], ss, mean, rstd, self.groups, net.eps)
-        return (ss, mean, rstd) if full else ss
+        return ss
 
-    def fwd_later(self, x):
-        """silu(gn(x)) for a weight gradient of the backward pass, computed on the weight-gradient side stream right before the grouped launch
-        that reads it (UNet2DModel.gn_later): the training forward folds the normalisation into the convolution's loader, so this tensor is
-        needed by nobody else and never sits on the critical path."""
-        y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-        self.net.gn_later(self, x, y)
-        return y
-
-    def _fwd_now(self, x, y):
-        B = x.shape[0]
-        mean = torch.empty(B * self.groups, device=x.device, dtype=torch.float32)
-        ops.groupnorm_fwd(x, self.net.P[self.prefix + ".weight"], self.net.P[self.prefix + ".bias"], y, mean, torch.empty_like(mean),
-                          self.groups, self.net.eps, self.silu)
-
-    def stats_from_partials(self, part, tiles, B, HW, full=False):
+    def stats_from_partials(self, part, tiles, B, HW):
         """stats() of a tensor whose producing convolution left its per-tile channel sums in `part` (vd_gemm_desc.gn_part)."""
         net = self.net
         ss = torch.empty((B, self.ch, 2), device=part.device, dtype=torch.float32)
@@ -326,7 +311,7 @@ class _Norm:
         rstd = torch.empty_like(mean)
         ops.groupnorm_stats_from_partials(part, tiles, net.P[self.prefix + ".weight"], net.P[self.prefix + ".bias"], ss, mean, rstd, HW,
                                           self.groups, net.eps)
-        return (ss, mean, rstd) if full else ss
+        return ss
 
     def bwd(self, dy, x, mean, rstd, dx, extra=None, extra2=None, rowsum=None, dx_ps=None):
         """extra / extra2: residual gradients added into dx; rowsum ([B, C] view, row stride free): per-image channel sums of the dx
@@ -424,56 +409,6 @@ class _Resnet:
             else:
                 self.conv2.fwd(h1, out, residual=x, gn_ss=ss2)
             return None
-        if save and net.fold_gn_train and fuse and _pairs(net) and not net.defer_gn_fwd and ops.gn_fusable(x, self.cout) \
-                and self.cin % 32 == 0 and self.cout % 32 == 0 and self.cin * H * W // net.groups <= 12288 \
-                and self.cout * H * W // net.groups <= 12288:
-            # Training forward without a normalise pass (round 4): the persistent convolution's loader applies GroupNorm + SiLU (as in the no-grad
-            # path) and WRITES the normalised activation it computes anyway (vd_gemm_desc.act_out) -- the operand the weight gradient needs;
-            # norm2's statistics come out of conv1's epilogue (gn_part), norm1's from a statistics pass (one read).  Per resnet: two normalise
-            # passes (read + write each) become one read; mean / rstd saved for the backward are the ones the forward used.
-            tiles = (H * W) // 256
-            ss1, m1, r1 = self.norm1.stats(x, full=True)
-            a1 = torch.empty((B, self.cin, H, W), device=dev, dtype=torch.float32)
-            h1 = torch.empty((B, self.cout, H, W), device=dev, dtype=torch.float32)
-            part = torch.empty((B, tiles, self.cout, 2), device=dev, dtype=torch.float32) if tiles > 0 else None
-            self.conv1.fwd(x, h1, rowadd=st.temb_all[:, self.temb_off:], rowadd_bstride=st.temb_all.stride(0), gn_ss=ss1, gn_part=part, act_out=a1)
-            wrote_a1, wrote_part = ops.ACT_OUT_WRITTEN, part is not None and ops.GN_PART_WRITTEN
-            if not wrote_a1:                                      # (a grid the persistent kernel does not take: small batches)
-                m1, r1 = self.norm1.fwd(x, a1)
-            if wrote_part:
-                ss2, m2, r2 = self.norm2.stats_from_partials(part, tiles, B, H * W, full=True)
-            else:
-                ss2, m2, r2 = self.norm2.stats(h1, full=True)
-            a2 = torch.empty_like(h1)
-            if self.has_sc:
-                ops.conv1x1(x, net.P[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin),
-                            net.P[self.prefix + ".conv_shortcut.bias"], out,
-                            a_packed=_bx3_packed_1x1(net, self.prefix + ".conv_shortcut", False, self.cout, self.cin, H * W, B))
-                self.conv2.fwd(h1, out, residual=out, gn_ss=ss2, act_out=a2)
-            else:
-                self.conv2.fwd(h1, out, residual=x, gn_ss=ss2, act_out=a2)
-            if not ops.ACT_OUT_WRITTEN:
-                m2, r2 = self.norm2.fwd(h1, a2)
-            return (x, a1, m1, r1, h1, a2, m2, r2)
-        if save and net.defer_gn_fwd and fuse and _split(net) and ops.gn_fusable(x, self.cout) \
-                and self.cin % 32 == 0 and self.cout % 32 == 0 and self.cin * H * W // net.groups <= 12288 \
-                and self.cout * H * W // net.groups <= 12288:
-            # training forward (round 4): GroupNorm + SiLU folded into the convolutions' loaders as in the no-grad path -- a statistics pass (one
-            # read) instead of the normalise pass (read + write) on the critical path; bit-identical activations (the folded loader evaluates the
-            # same expression on the same scale / shift pairs).  silu(gn(.)) itself is only an operand of the WEIGHT gradients: it is recomputed
-            # on their side stream in the backward pass (_Norm.fwd_later), where the HBM-bound pass runs beside MFMA-bound kernels.
-            ss1, m1, r1 = self.norm1.stats(x, full=True)
-            h1 = torch.empty((B, self.cout, H, W), device=dev, dtype=torch.float32)
-            self.conv1.fwd(x, h1, rowadd=st.temb_all[:, self.temb_off:], rowadd_bstride=st.temb_all.stride(0), gn_ss=ss1)
-            ss2, m2, r2 = self.norm2.stats(h1, full=True)
-            if self.has_sc:
-                ops.conv1x1(x, net.P[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin),
-                            net.P[self.prefix + ".conv_shortcut.bias"], out,
-                            a_packed=_bx3_packed_1x1(net, self.prefix + ".conv_shortcut", False, self.cout, self.cin, H * W, B))
-                self.conv2.fwd(h1, out, residual=out, gn_ss=ss2)
-            else:
-                self.conv2.fwd(h1, out, residual=x, gn_ss=ss2)
-            return (x, None, m1, r1, h1, None, m2, r2)
         ps = (save and self.ps_plan(B, H, W)) or ps_ng
         # The shortcut (a 1x1 convolution of x, HBM-bound) does not depend on the norm1 -> conv1 -> norm2 chain: with net.sc_stream it runs on an
         # auxiliary stream beside those kernels and is joined before conv2 adds it as the residual
@@ -520,9 +455,6 @@ class _Resnet:
         dev = x.device
         if isinstance(a2, ops.PreSplit):
             return self._bwd_ps(saved, dout, dx, st, dout_rs, extra2, dx_rs, dout_ps, dx_ps)
-        if a2 is None:                                        # folded-GroupNorm forward: the weight gradients' operands are made on their side stream
-            a2 = self.norm2.fwd_later(h1)
-            a1 = self.norm1.fwd_later(x)
         # conv2 (+ shortcut bias: both biases receive rowsum(dout))
         if dout_rs is None:
             bias_ws = net.scratch_bc(B, self.cout).view(B, self.cout)
@@ -977,16 +909,6 @@ class UNet2DModel(nn.Module):
         # no-grad forward: the statistics of a ResnetBlock2D's second GroupNorm are summed in the first convolution's epilogue
         # (vd_gemm_desc.gn_part) instead of a read of its output; False: the statistics pass
         self.gn_stats_in_epilogue = os.environ.get("VILLAN_GN_STATS_IN_EPILOGUE", "1") != "0"
-        # opt-in (round 4, measured and NOT the default): training forward with GroupNorm + SiLU folded into the 16x16 / 32x32 convolutions'
-        # loaders; silu(gn(.)) for the weight gradients is recomputed on the side stream in the backward pass.  Bit-identical results, 1.7 GB
-        # less saved activations at B = 128, but 18.07 -> 18.44 ms per step (profiles/r04_gn_defer_ab.txt): the statistics pass plus the
-        # recomputation move MORE bytes than the normalise pass they replace, and on a power-bound chip an HBM-bound pass running beside the
-        # MFMA-bound kernels is not free (the clock drops for both)
-        self.defer_gn_fwd = os.environ.get("VILLAN_DEFER_GN_FWD", "0") != "0"
-        # round 4: training forward of the 16x16 / 32x32 resnets without normalise passes -- the convolution's GroupNorm-folding loader writes
-        # silu(gn(x)) as a side output, norm2's statistics come from conv1's epilogue.  Opt-in: measured +0.2 ms / step (profiles/r04_gn_actout_ab.txt)
-        self.fold_gn_train = os.environ.get("VILLAN_FOLD_GN_TRAIN", "0") != "0"
-        self._gn_jobs = []
         self._pk_jobs = []
         # "bf16x3": eligible 3x3 convolutions (forward and stride-1 input gradient at 8x8 / 16x16 / 32x32) run on the bf16 matrix
         # cores as hi*hi + hi*lo + lo*hi with f32 accumulation (~1e-5 of the exact result); "f32": everything on the exact f32 MFMA.
@@ -1117,10 +1039,6 @@ class UNet2DModel(nn.Module):
                 if self.wgrad_stream and self.wgrad_flush_jobs and sum(len(v) for v in self._wg_jobs.values()) >= self.wgrad_flush_jobs:
                     self._wg_flush()
                 return
-        if self._gn_jobs:                                     # an ungrouped weight gradient runs NOW: its operand may be a deferred silu(gn(.))
-            for norm, xx, yy in self._gn_jobs:
-                norm._fwd_now(xx, yy)
-            self._gn_jobs = []
         ops.conv_wgrad(dy, x, dw2d, mode, self.wgrad_ws, accumulate=True, pad=pad, math_mode=math_mode)
 
     # ---- auxiliary stream: independent HBM-bound launches (the 1x1 shortcut and its input gradient) beside the 3x3 chain of a ResnetBlock ----
@@ -1163,13 +1081,6 @@ class UNet2DModel(nn.Module):
             ops.presplit_pack(t, out=out)
         return out
 
-    def gn_later(self, norm, x, y):
-        """y = norm(x) (+SiLU) before the next grouped weight-gradient launch, on its stream (see _Norm.fwd_later)."""
-        if self.wgrad_stream and self.group_wgrad:
-            self._gn_jobs.append((norm, x, y))
-        else:
-            norm._fwd_now(x, y)
-
     def rowsum(self, x, ws, ws_ld=None):
         """Bias-gradient partials ws[b][m] = sum_p x[b][m][p]: consumed only when the bucket is flushed, so with the side stream they
         ride there too (x is a dY of a queued weight gradient or is kept referenced like one)."""
@@ -1179,7 +1090,7 @@ class UNet2DModel(nn.Module):
             ops.rowsum(x, ws, ws_ld=ws_ld)
 
     def _wg_flush(self):
-        if not any(self._wg_jobs.values()) and not self._rs_jobs and not self._gn_jobs and not self._pk_jobs:
+        if not any(self._wg_jobs.values()) and not self._rs_jobs and not self._pk_jobs:
             return
         if self.wgrad_stream:
             # Weight gradients are off the critical path of the backward pass: run the grouped launches on a SIDE stream so that they
@@ -1193,21 +1104,17 @@ class UNet2DModel(nn.Module):
             with torch.cuda.stream(self._wg_side):
                 for t, out in self._pk_jobs:                   # dY operands whose producer wrote f32 only -> pre-split images
                     ops.presplit_pack(t, out=out)
-                for norm, x, y in self._gn_jobs:               # operands of the queued weight gradients (folded-GroupNorm forward)
-                    norm._fwd_now(x, y)
                 for x, ws, ld in self._rs_jobs:
                     ops.rowsum(x, ws, ws_ld=ld)
                 for cls, jobs in self._wg_jobs.items():
                     if jobs:
                         ops.conv_wgrad_group([j[0] for j in jobs], self._dev)
-            self._wg_keep.append((self._wg_jobs, self._rs_jobs, self._gn_jobs, self._pk_jobs))
-            self._rs_jobs, self._gn_jobs, self._pk_jobs = [], [], []
+            self._wg_keep.append((self._wg_jobs, self._rs_jobs, self._pk_jobs))
+            self._rs_jobs, self._pk_jobs = [], []
         else:
             for t, out in self._pk_jobs:
                 ops.presplit_pack(t, out=out)
-            for norm, x, y in self._gn_jobs:
-                norm._fwd_now(x, y)
-            self._gn_jobs, self._pk_jobs = [], []
+            self._pk_jobs = []
             for cls, jobs in self._wg_jobs.items():
                 if jobs:
                     ops.conv_wgrad_group([j[0] for j in jobs], self._dev)
@@ -1282,7 +1189,7 @@ class UNet2DModel(nn.Module):
         # a backward pass that raised midway leaves queued weight-gradient / row-sum jobs behind: they must never run in THIS pass
         if self._wg_keep:
             self._wg_join()
-        self._wg_jobs, self._rs_jobs, self._gn_jobs, self._pk_jobs = {}, [], [], []
+        self._wg_jobs, self._rs_jobs, self._pk_jobs = {}, [], []
         if self._wt_buf is None:
             self._wt_buf = torch.empty(self._wt_total, device=self._dev, dtype=torch.float32)
         self._wt_fresh = set()
