@@ -6,12 +6,12 @@ import math
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
 from villandiffusion_amd import ops  # noqa: E402
 from villandiffusion_amd.lib import A_COL, B_CONV3, B_CONV3_T, B_CONV3_UP, B_PLAIN  # noqa: E402
+from exact_ref import conv_f64, wgrad_f64  # noqa: E402
 
 DEV = "cuda"
 EXACT = 1e-5            # f32 accumulation against f64, relative to the output scale
@@ -29,33 +29,6 @@ def rel(a, b):
 
 def r16(t):
     return t.bfloat16().double()
-
-
-def conv_f64(x, w, mode, chunk=16):
-    """float64 3x3 convolution (padding 1) on the GPU: im2col + matmul; mode B_CONV3_UP upsamples x by nearest 2x first."""
-    x, w = x.to(DEV).double(), w.to(DEV).double()
-    if mode == B_CONV3_UP:
-        x = F.interpolate(x, scale_factor=2.0, mode="nearest")
-    B, _, H, W = x.shape
-    wm = w.reshape(w.shape[0], -1)
-    out = torch.empty(B, w.shape[0], H, W, device=DEV, dtype=torch.float64)
-    for b0 in range(0, B, chunk):
-        cols = F.unfold(x[b0:b0 + chunk], 3, padding=1)                      # [b, C*9, HW]
-        out[b0:b0 + chunk] = torch.matmul(wm, cols).view(-1, w.shape[0], H, W)
-    return out
-
-
-def wgrad_f64(dy, x, mode, taps=9, chunk=16):
-    """dW[m, c*9 + t] = sum_{b,p} dy[b,m,p] * im2col(x)[b, c*9 + t, p] in float64 on the GPU."""
-    dy, x = dy.to(DEV).double(), x.to(DEV).double()
-    if mode == B_CONV3_UP:
-        x = F.interpolate(x, scale_factor=2.0, mode="nearest")
-    B, M = dy.shape[:2]
-    acc = 0
-    for b0 in range(0, B, chunk):
-        cols = F.unfold(x[b0:b0 + chunk], 3, padding=1) if taps == 9 else x[b0:b0 + chunk].flatten(2)
-        acc = acc + torch.einsum("bmp,bkp->mk", dy[b0:b0 + chunk].flatten(2), cols)
-    return acc
 
 
 # B, Cin, Cout, output side, mode, tile
