@@ -146,7 +146,8 @@ int vd_gemm(const vd_gemm_desc* desc, void* stream);
 int64_t vd_gemm_ws_floats(const vd_gemm_desc* desc);
 /* Kernel vd_gemm will use for this problem: 1: 128x128, 2: 64x128, 3: 64x64 gather tiles, 4 / 6: patch-staged 3x3
  * convolution kernel with 128x128 / 128x256 tiles, 5: plain GEMM kernel, 7: direct 3x3 convolution for <= 4 output
- * channels, 8 / 9 / 10: split-precision bf16 3x3 convolution / plain product (a_packed) / activation product (math = 1), 11: the persistent
+ * channels (VD_B_CONV3, and VD_B_CONV3_T without a_packed: the input gradient of a convolution with <= 4 INPUT channels, A being the
+ * [C_in][C_out * 9] transposed copy of vd_weight_transpose, W % 4 == 0, C >= 16, 16-byte aligned B / D and strides), 8 / 9 / 10: split-precision bf16 3x3 convolution / plain product (a_packed) / activation product (math = 1), 11: the persistent
  * variant of 9 (grids of >= 1024 tiles), 12 / 15 / 16: the 128 x 256 / 128 x 512 / split 128 x 256 tiles of 8, 13: the 128 x 256 tile of 9,
  * 18: the persistent 16x16x32-MFMA 3x3 convolution (32-channel K-steps, 128 x 256 tiles, LDS-DMA weight stages, 8 x 32 pixel
  * segments of images of any size), 19: the persistent 16x16x32 kernel for 9's problems, 20 (round 6): the whole-K 16x16x32 kernel of the 8x8 level
@@ -383,6 +384,12 @@ int vd_mse_fwd_bwd(const float* pred, const float* y, const float* pscale, float
 #define VD_LOSS_HUBER 2
 int vd_loss_fwd_bwd(const float* pred, const float* y, const float* pscale, float* dpred, float* loss,
                     float* partial, int B, int64_t chw, float gscale, int kind, void* stream);
+/* Trigger-inversion objective (distribution shift, Elijah): r = mean_b e[b] - lambda * tau, *loss = L = ||r||_2 over the chw elements,
+ * dout[b] = r / (B L) for every b (the gradient of L with respect to e, contiguous [B, chw]) and dtau = -lambda r / L (the direct term of
+ * dL/dtau; the term through the network is the sum over b of the network's input gradient).  e: [B, chw] with batch stride e_bstride >= chw;
+ * tau, dtau: [chw]; partial: >= 1024 floats.  Two-phase sum in a fixed order (no atomics): bit-reproducible.  L == 0: zero gradients. */
+int vd_trigger_inv_objective(const float* e, const float* tau, float lambda, float* loss, float* dout, float* dtau, float* partial,
+                             int B, int64_t chw, int64_t e_bstride, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K9 -- global grad-norm clip + Adam on flat buffers (VillanDiffusion.py:445,1165-1169).

@@ -433,6 +433,56 @@ extern "C" int vd_l2norm_sq(const float* g, int64_t n, float* partial, float* ou
     return 0;
 }
 
+// ---- trigger-inversion objective (defense.py): L = || mean_b e[b] - lambda * tau ||_2 over the C*H*W elements, and its gradients --------------
+// Phase 1: r[i] = mean_b e[b][i] - lambda * tau[i] (the batch sum in double: B is not bounded), parked in dtau; partial[block] = the block's sum
+// of r^2.  Phase 2: every block adds the partials in index order (the same value in every block and in every run: no atomics), then
+// dout[b][i] = r / (B L) for every b and dtau[i] = -lambda r / L.  L = 0: zero gradients.
+__global__ __launch_bounds__(256) void trigger_inv_residual_kernel(const float* __restrict__ e, const float* __restrict__ tau, float* __restrict__ r,
+                                                                    float* __restrict__ partial, int B, int64_t n, int64_t e_bstride, float lambda) {
+    __shared__ float red[4];
+    float s = 0.f;
+    GRID_STRIDE(i, n) {
+        double m = 0.0;
+        for (int b = 0; b < B; ++b) m += (double)e[(int64_t)b * e_bstride + i];
+        const float v = (float)(m / (double)B) - lambda * tau[i];
+        r[i] = v;
+        s += v * v;
+    }
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void trigger_inv_grad_kernel(const float* __restrict__ partial, int n_partial, float* __restrict__ loss,
+                                                                float* __restrict__ dout, float* __restrict__ dtau, int B, int64_t n, float lambda) {
+    __shared__ float Ls;
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int k = 0; k < n_partial; ++k) s += (double)partial[k];
+        Ls = (float)sqrt(s);
+    }
+    __syncthreads();
+    const float L = Ls;
+    const float inv = L > 0.f ? 1.0f / L : 0.f;
+    const float inv_b = inv / (float)B;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *loss = L;
+    GRID_STRIDE(i, n) {
+        const float v = dtau[i];
+        const float g = v * inv_b;
+        for (int b = 0; b < B; ++b) dout[(int64_t)b * n + i] = g;
+        dtau[i] = -lambda * (v * inv);
+    }
+}
+
+extern "C" int vd_trigger_inv_objective(const float* e, const float* tau, float lambda, float* loss, float* dout, float* dtau, float* partial,
+                                        int B, int64_t chw, int64_t e_bstride, void* stream) {
+    VD_REQUIRE(e && tau && loss && dout && dtau && partial && B > 0 && chw > 0 && e_bstride >= chw, "vd_trigger_inv_objective: bad args");
+    int grid = egrid(chw);
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(trigger_inv_residual_kernel, dim3(grid), dim3(256), 0, ST, e, tau, dtau, partial, B, chw, e_bstride, lambda);
+    hipLaunchKernelGGL(trigger_inv_grad_kernel, dim3(grid), dim3(256), 0, ST, partial, grid, loss, dout, dtau, B, chw, lambda);
+    VD_LAUNCH_CHECK("vd_trigger_inv_objective");
+    return 0;
+}
+
 extern "C" int vd_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* norm_sq, float max_norm,
                             float inv_scale, float lr, float beta1, float beta2, float eps, int step, unsigned* skipped, void* stream) {
     VD_REQUIRE(p && g && m && v && n > 0 && step >= 1, "vd_adam_step: bad args");

@@ -907,7 +907,10 @@ __global__ __launch_bounds__(256) void conv3_smallm_kernel(const vd_gemm_desc d)
 // pixels (the float4 is aligned, straight from global memory; the two edge pixels come from the neighbouring lanes' registers) and the 27
 // weights arrive as scalar loads (wave-uniform address): 9 loads feed 36 * M FMAs, against 18 LDS reads per 9 * M FMAs in the kernel
 // above, which is LDS-issue bound (85 us at B = 128 for a 17 us read of the input).  W % 4 == 0.
-template <int MM, int NW>
+// FLIP: the input gradient of a convolution with <= 4 INPUT channels (conv_in: dY[128] -> dX[3]), VD_B_CONV3_T.  A is the transposed copy
+// [c_in][c_out * 9] every VD_B_CONV3_T caller hands over; the taps are read back to front (tap (r, s) meets the pixel at (+1 - r, +1 - s)), the
+// rest -- loads, channel split over the waves, the fixed-order sum -- is the same code.
+template <int MM, int NW, bool FLIP = false>
 __global__ __launch_bounds__(64 * NW) void conv3_fewout_kernel(const vd_gemm_desc d, int64_t quads) {
     __shared__ float red[NW - 1][MM][4][64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -959,7 +962,7 @@ __global__ __launch_bounds__(64 * NW) void conv3_fewout_kernel(const vd_gemm_des
                 for (int r = 0; r < 3; ++r)
 #pragma unroll
                     for (int q3 = 0; q3 < 3; ++q3) {
-                        const float w = wm[r * 3 + q3];
+                        const float w = wm[FLIP ? 8 - (r * 3 + q3) : r * 3 + q3];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) acc[m][j] = fmaf(w, e[r][q3 + j], acc[m][j]);
                     }
@@ -999,6 +1002,11 @@ static bool fewout_eligible(const vd_gemm_desc& d) {
 }
 
 static bool smallm_eligible(const vd_gemm_desc& d) {
+    if (d.b_mode == VD_B_CONV3_T) {                          // flipped taps: the no-LDS kernel only (no shape the LDS-patch kernel alone would take)
+        if (d.a_mode != VD_A_ROW || d.M > 4 || d.tile != 0 || d.debug != 0 || d.act || d.bias || d.pool2 || d.b_presplit) return false;
+        if (d.rowadd || d.residual || d.d_trans || d.accumulate || d.bias_on_n || d.nb2 > 1 || d.a_bstride != 0 || d.gn_ss) return false;
+        return d.OH == d.H && d.OW == d.W && d.lda == d.K && d.K == d.C * 9 && fewout_eligible(d);
+    }
     if (d.b_mode != VD_B_CONV3 || d.a_mode != VD_A_ROW || d.M > 4 || d.tile != 0 || d.debug != 0 || d.act) return false;
     if (d.rowadd || d.residual || d.d_trans || d.accumulate || d.bias_on_n || d.nb2 > 1 || d.a_bstride != 0 || d.gn_ss) return false;
     if (d.OH != d.H || d.OW != d.W) return false;
@@ -1008,6 +1016,11 @@ static bool smallm_eligible(const vd_gemm_desc& d) {
 
 static int launch_smallm(const vd_gemm_desc& d, hipStream_t st) {
     const int nb = d.N / d.NP;
+    if (d.b_mode == VD_B_CONV3_T) {
+        const int64_t quads = (int64_t)nb * d.H * (d.W / 4);
+        hipLaunchKernelGGL((conv3_fewout_kernel<4, 8, true>), dim3((unsigned)((quads + 63) / 64)), dim3(512), 0, st, d, quads);
+        return 0;
+    }
     if (fewout_eligible(d)) {
         const int64_t quads = (int64_t)nb * d.H * (d.W / 4);
         // eight waves per 256 pixels (round 6; four until then): 31 against 48 us for conv_out at B = 128 -- the loop is a latency chain (loads -> 100 FMAs per

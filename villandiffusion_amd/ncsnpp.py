@@ -144,6 +144,8 @@ class _AttnPP:
 class NCSNppModel(UNet2DModel):
     """Drop-in for ``diffusers.UNet2DModel`` in its NCSN++ configuration (time_embedding_type='fourier', Skip blocks)."""
 
+    _input_grad = False                                       # its backward (below) yields parameter gradients only: no sample gradient, no input-gradient pass
+
     def __init__(self, in_channels=3, out_channels=3, sample_size=32, block_out_channels=(128, 256, 256, 256),
                  down_block_types=("SkipDownBlock2D", "AttnSkipDownBlock2D", "SkipDownBlock2D", "SkipDownBlock2D"),
                  up_block_types=("SkipUpBlock2D", "SkipUpBlock2D", "AttnSkipUpBlock2D", "SkipUpBlock2D"), layers_per_block=4,

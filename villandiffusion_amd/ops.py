@@ -341,7 +341,9 @@ def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bs
         name = f"gemm_plain_kernel<{a_mode}>"
     elif tl == 7:
         few = d.W % 4 == 0 and d.C >= 16 and d.b_bstride % 4 == 0 and d.d_bstride % 4 == 0 and d.ldd % 4 == 0      # fewout_eligible() of vd_gemm.hip
-        name = "conv3_fewout_kernel<4, 8>" if few else f"conv3_smallm_kernel<{32 if d.W % 32 == 0 else 16}, 4>"
+        # (B_CONV3_T: the flipped-tap form, conv_in's input gradient -- it has no LDS-patch partner)
+        name = (f"conv3_fewout_kernel<4, 8, {'true' if b_mode == B_CONV3_T else 'false'}>" if few or b_mode == B_CONV3_T
+                else f"conv3_smallm_kernel<{32 if d.W % 32 == 0 else 16}, 4>")
     else:
         name = f"gemm_kernel<{_TILE_NAMES[tl]},{'ROW' if a_mode == A_ROW else 'COL'},{_B_NAMES[b_mode]}>"
     _PROF.append({"name": name, "flops": flops, "bytes": nbytes, "e0": e0, "e1": e1, "kind": "mfma", "shape": (M, K, d.NP, N // d.NP, d.OH, d.OW)})
@@ -1039,6 +1041,19 @@ def mse_fwd_bwd(pred, y, dpred, loss, partial, pscale=None, gscale=1.0, kind="l2
     return loss
 
 
+def trigger_inv_objective(e, tau, lam, loss, dout, dtau, partial):
+    """loss = || mean_b e[b] - lam * tau ||_2, dout[b] = dloss/de[b] (every b) and dtau = the direct term -lam * r / loss, in one call
+    (vd_trigger_inv_objective: fixed-order two-phase sum, bit-reproducible; loss == 0 gives zero gradients)."""
+    Bn, Cc, H, W, ebs = _img(e)
+    chw = Cc * H * W
+    assert tau.is_contiguous() and tau.numel() == chw and dtau.is_contiguous() and dtau.numel() == chw and tau.dtype == dtau.dtype == torch.float32
+    assert dout.is_contiguous() and dout.shape == e.shape and dout.dtype == torch.float32 and partial.numel() >= 1024 and loss.numel() >= 1
+    _timed("trigger_inv_objective (trigger_inv_residual_kernel + trigger_inv_grad_kernel)", 4.0 * (2 * e.numel() + 3 * chw), "hbm", lambda: L.check(
+        _lib().vd_trigger_inv_objective(_p(e), _p(tau), float(lam), _p(loss), _p(dout), _p(dtau), _p(partial), Bn, chw, ebs, _s()),
+        "vd_trigger_inv_objective"))
+    return loss
+
+
 def l2norm_sq(g, partial, out_sq):
     assert g.is_contiguous() and partial.numel() >= 1024
     _timed("l2norm_sq (sumsq_kernel)", 4.0 * g.numel(), "hbm",
@@ -1046,9 +1061,11 @@ def l2norm_sq(g, partial, out_sq):
     return out_sq
 
 
-def adam_step(p, g, m, v, norm_sq, max_norm, inv_scale, lr, beta1, beta2, eps, step, skipped=None):
+def adam_step(p, g, m, v, norm_sq, max_norm, inv_scale, lr, beta1, beta2, eps, step, skipped=None, weights=True):
+    """weights=False: `p` is no network parameter (an inverted trigger): caches derived from the weights stay valid."""
     global WEIGHTS_EPOCH
-    WEIGHTS_EPOCH += 1
+    if weights:
+        WEIGHTS_EPOCH += 1
     _timed("adam_step (adam_kernel)", 28.0 * p.numel(), "hbm", lambda: L.check(      # p, g, m, v read; p, m, v written
         _lib().vd_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(norm_sq), max_norm, inv_scale, lr, beta1, beta2,
                             eps, step, _p(skipped), _s()), "vd_adam_step"))

@@ -685,6 +685,9 @@ class _Attn:
 
 # ----------------------------------------------------------------------------------------------------------- network
 class _UNetFn(torch.autograd.Function):
+    """`anchor` is the network's stand-in for its parameters in the autograd graph (their gradients are a side effect of backward, written into
+    the flat gradient buffer); None: the weights are frozen and only the sample's gradient is wanted (the input-gradient pass)."""
+
     @staticmethod
     def forward(ctx, net, x, t, anchor):
         out, st = net._run_forward(x, t, save=True)
@@ -692,15 +695,25 @@ class _UNetFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
-        ctx.net._run_backward(ctx.st, dout.contiguous())
+        net, st = ctx.net, ctx.st
         ctx.st = None
-        return None, None, None, None
+        if not net._input_grad:                               # (subclasses with a backward of their own: weights only, as ever)
+            net._run_backward(st, dout.contiguous())
+            return None, None, None, None
+        dx = net._run_backward(st, dout.contiguous(), want_dx=ctx.needs_input_grad[1], weights=ctx.needs_input_grad[3])
+        return None, dx, None, None
 
 
 class UNet2DModel(nn.Module):
     """Drop-in for ``diffusers.UNet2DModel`` (positional time embedding; DownBlock2D/AttnDownBlock2D/UpBlock2D/
     AttnUpBlock2D) on MI355X."""
+
+    # forward() differentiates with respect to the SAMPLE as well (a sample that requires grad gets .grad; with every parameter frozen the
+    # backward is the input-gradient pass, see _run_backward).  Subclasses with a backward of their own switch it off.
+    _input_grad = True
+    _dx_only = False                                          # True inside an input-gradient pass: wgrad / rowsum / colsum_later / pack_later queue nothing
 
     def __init__(self, in_channels=3, out_channels=3, sample_size=32, block_out_channels=(128, 256, 256, 256),
                  down_block_types=("DownBlock2D", "AttnDownBlock2D", "DownBlock2D", "DownBlock2D"),
@@ -852,6 +865,8 @@ class UNet2DModel(nn.Module):
             if name.endswith(".weight") and len(shape) == 4 and shape[2] == 3 and name != "conv_in.weight":
                 self._wt_offs[name[:-7]] = wt_total
                 wt_total += int(math.prod(shape))
+        self._wt_offs["conv_in"] = wt_total                     # (last: read only by a pass that wants the sample's gradient)
+        wt_total += int(math.prod(offs["conv_in.weight"][2]))
         self._wt_total = wt_total
         self._wt_buf: Optional[torch.Tensor] = None
         self.wgrad_ws: Optional[torch.Tensor] = None
@@ -1016,6 +1031,8 @@ class UNet2DModel(nn.Module):
 
     def colsum_later(self, ws, out, B, Cc, ld=None):
         """out[c] += sum_b ws[b*ld + c], executed at the next _cs_flush() (ws must stay untouched until then)."""
+        if self._dx_only:
+            return
         ld = Cc if ld is None else ld
         wp, op = ws.data_ptr(), out.data_ptr()
         for c0 in range(0, Cc, 64):
@@ -1027,6 +1044,8 @@ class UNet2DModel(nn.Module):
     # and off the critical path of the backward pass, so they are queued (operands kept alive) and run as a few grouped launches when
     # the bucket is final.
     def wgrad(self, dy, x, dw2d, mode, pad=0, math_mode=0):
+        if self._dx_only:
+            return
         if math_mode == 1 and self.group_wgrad:
             d = ops.wgrad_desc(dy, x, dw2d, mode, None, accumulate=True, pad=pad, math_mode=1)
             if self.conv_math == "bf16":                      # one bf16 product per term where a grouped kernel has that switch (its own class)
@@ -1074,6 +1093,8 @@ class UNet2DModel(nn.Module):
     def pack_later(self, t):
         """The pre-split image of `t` (a dY whose producer wrote f32 only) for a queued pre-split weight gradient: packed on the weight-gradient
         stream right before the grouped launch that reads it (off the critical path), or now when there is no such stream."""
+        if self._dx_only:                                     # (its only readers are weight gradients)
+            return None
         out = ops.presplit_empty(t.shape, t.device)
         if self.wgrad_stream and self.group_wgrad:
             self._pk_jobs.append((t, out))
@@ -1084,6 +1105,8 @@ class UNet2DModel(nn.Module):
     def rowsum(self, x, ws, ws_ld=None):
         """Bias-gradient partials ws[b][m] = sum_p x[b][m][p]: consumed only when the bucket is flushed, so with the side stream they
         ride there too (x is a dY of a queued weight gradient or is kept referenced like one)."""
+        if self._dx_only:
+            return
         if self.wgrad_stream and self.group_wgrad:
             self._rs_jobs.append((x, ws, ws_ld))
         else:
@@ -1185,7 +1208,7 @@ class UNet2DModel(nn.Module):
             self._wt_fresh.add(prefix)
         return self._wt_buf[off:off + M * Cc * T].view(Cc, M * T)
 
-    def _prepare_backward(self, B):
+    def _prepare_backward(self, B, weights=True):
         # a backward pass that raised midway leaves queued weight-gradient / row-sum jobs behind: they must never run in THIS pass
         if self._wg_keep:
             self._wg_join()
@@ -1193,6 +1216,8 @@ class UNet2DModel(nn.Module):
         if self._wt_buf is None:
             self._wt_buf = torch.empty(self._wt_total, device=self._dev, dtype=torch.float32)
         self._wt_fresh = set()
+        if not weights:                                         # input-gradient pass: no weight-gradient workspace
+            return
         if self.wgrad_ws is None or getattr(self, "_ws_B", None) != B:
             need = 0
             S = self.sample_size
@@ -1232,7 +1257,9 @@ class UNet2DModel(nn.Module):
             t = t[None]
         t = t.to(torch.float32).expand(B).contiguous()
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            out = _UNetFn.apply(self, x, t, self._anchor)
+            out = _UNetFn.apply(self, x, t, self._anchor)     # (a sample that requires grad gets its gradient from the same pass)
+        elif torch.is_grad_enabled() and self._input_grad and x.requires_grad:
+            out = _UNetFn.apply(self, x, t, None)             # frozen weights: the input-gradient pass
         else:
             out, _ = self._run_forward(x, t, save=False)
         if return_dict:
@@ -1370,10 +1397,26 @@ class UNet2DModel(nn.Module):
             st.up_slots, st.cats = up_slots, cats
         return out, st
 
-    def _run_backward(self, st, dout):
+    def _run_backward(self, st, dout, want_dx=False, weights=True):
+        """The explicit backward pass.  weights: parameter gradients accumulate into the flat gradient (deferred weight gradients and bias sums on the
+        side stream, the time-embedding MLP, the bucket hook).  want_dx: ALSO conv_in's input gradient -- the return value, dL/dsample.
+        weights=False is the input-gradient pass of a frozen network: the same tape, the same kernels on the main stream (so the same dx, bit for
+        bit), and nothing of the above -- no weight gradient, pack, row- or column-sum job is queued, the time-embedding MLP is not differentiated
+        (timesteps are not differentiable), flat_grad, the side stream and bucket_ready_hook are never touched."""
+        if not weights:
+            if not want_dx:
+                return None
+            self._dx_only = True
+            try:
+                return self._backward_tape(st, dout, True, False)
+            finally:
+                self._dx_only = False
+        return self._backward_tape(st, dout, want_dx, True)
+
+    def _backward_tape(self, st, dout, want_dx, weights):
         dev = self._dev
         B = st.B
-        self._prepare_backward(B)
+        self._prepare_backward(B, weights)
         self._cs_begin(B)
         st.d_temb_all = self._d_temb_buffer(B)
         up_slots = st.up_slots
@@ -1407,7 +1450,8 @@ class UNet2DModel(nn.Module):
         self.norm_out.bwd(da, final, mo, ro, g, rowsum=g_rs, dx_ps=g_ps)
         # `g` is the gradient wrt the output of the most recent forward op; walk the tape backwards.
         slot = n_skip
-        hook = self.bucket_ready_hook
+        hook = self.bucket_ready_hook if weights else None
+        dx_in = None
         while sv:
             if hook is not None:                                  # gradient buckets complete in the order up|out, mid, down
                 if len(sv) == st.marks["mid_end"]:
@@ -1448,9 +1492,13 @@ class UNet2DModel(nn.Module):
                 layer.bwd(g, x, dx, bias_ws=g_rs)
                 g, g_rs, g_ps = self._add_skip_grad(dx, x, st, dcats), None, None
             elif kind == "conv_in":
-                self._conv_in.bwd(g, rec[1], None, bias_ws=g_rs)
+                if want_dx:
+                    dx_in = torch.empty(rec[1].shape, device=dev, dtype=torch.float32)
+                self._conv_in.bwd(g, rec[1], dx_in, bias_ws=g_rs)
             else:
                 raise RuntimeError(kind)
+        if not weights:
+            return dx_in
         self._cs_flush()                                          # d_temb_all's partials may sit on the side stream
         if hook is not None:
             hook(2)
@@ -1472,6 +1520,7 @@ class UNet2DModel(nn.Module):
         self._cs_flush()
         if hook is not None:
             hook(3)
+        return dx_in
 
     def _skip_grad(self, x, st, dcats):
         """If `x` is a skip tensor living in a concat buffer: the gradient that flowed into it through the up path (a channel
