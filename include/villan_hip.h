@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 11
+#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats: additions only, no existing prototype moved */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -390,6 +390,22 @@ int vd_loss_fwd_bwd(const float* pred, const float* y, const float* pscale, floa
  * tau, dtau: [chw]; partial: >= 1024 floats.  Two-phase sum in a fixed order (no atomics): bit-reproducible.  L == 0: zero gradients. */
 int vd_trigger_inv_objective(const float* e, const float* tau, float lambda, float* loss, float* dout, float* dtau, float* partial,
                              int B, int64_t chw, int64_t e_bstride, void* stream);
+/* Data-free backdoor-removal loss (mitigation.py): pred is [2B, chw] with batch stride pred_bstride >= chw -- rows 0..B-1 the model's output on
+ * eps, rows B..2B-1 its output on eps + tau; ref is the frozen teacher's output on eps, contiguous [B, chw].
+ *   clean = mean over B*chw of (pred[b] - ref[b])^2,  shift = mean over B*chw of (pred[B+b] - ref[b])^2,
+ *   terms[0..2] = {w_clean*clean + w_shift*shift, clean, shift},
+ *   dpred (contiguous [2B, chw]): dpred[b] = gscale*w_clean*2/(B*chw) * (pred[b] - ref[b]), dpred[B+b] the same with w_shift.
+ * One read of pred and ref, one write of dpred; 16-byte accesses where chw, the stride and the pointers allow, with the same sums either way.
+ * partial: >= 2048 floats.  Two-phase sum in a fixed order (no atomics): bit-reproducible. */
+int vd_removal_loss(const float* pred, const float* ref, float w_clean, float w_shift, float gscale, float* dpred, float* terms,
+                    float* partial, int B, int64_t chw, int64_t pred_bstride, void* stream);
+/* Statistics of an image set x [N, C, H, W] (batch stride x_bstride) after y = clamp(x*mul + add, lo, hi), every operation rounded on its own
+ * (vd_postprocess's values; lo = -inf, hi = +inf: no clamp).  Two passes: mean_img[C, H, W] = mean of y over N (sum in double); then
+ *   stats[0] = sum_i ||y_i - mean_img||^2   (the mean pairwise squared distance over i < j is 2/(N-1) * stats[0]),
+ *   stats[1] = sum_i TV(y_i),  TV(y) = sum_c ( sum |y[c,h+1,w] - y[c,h,w]| + sum |y[c,h,w+1] - y[c,h,w]| ).
+ * partial: >= 2048 floats.  Fixed-order sums (no atomics): bit-reproducible, and a strided view gives the bits of its contiguous copy. */
+int vd_image_set_stats(const float* x, int N, int C, int H, int W, int64_t x_bstride, float mul, float add, float lo, float hi,
+                       float* mean_img, float* stats, float* partial, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K9 -- global grad-norm clip + Adam on flat buffers (VillanDiffusion.py:445,1165-1169).

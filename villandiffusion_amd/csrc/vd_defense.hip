@@ -1,0 +1,232 @@
+// Backdoor mitigation (villandiffusion_amd/mitigation.py): the statistics of a sampled image set (Elijah's uniformity / total-variation features)
+// and the data-free removal loss with its gradient.  Both are HBM-bound reductions with sums in a fixed order (no atomics): a repeat is
+// bit-identical.  Compiled without FMA contraction: the post-processing rounds every operation on its own, as vd_postprocess does.
+//
+// Both kernels walk their elements in ITEMS of four consecutive floats.  Where rows and pointers are 16-byte aligned an item is one f32x4 access,
+// otherwise four scalar ones; which elements a thread owns and the order it adds them in do not depend on that choice, so a strided or unaligned
+// view gives the same bits as its contiguous copy.
+#include "vd_common.h"
+
+namespace {
+
+constexpr int MAXP = 1024;   // blocks of a reducing launch: partial[0 .. MAXP) and partial[MAXP .. 2 MAXP) hold one sum each
+
+inline int item_grid(int64_t items) {
+    int64_t g = (items + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > MAXP ? MAXP : g));
+}
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+#define ITEM_STRIDE(q, n) \
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < (n); q += (int64_t)gridDim.x * blockDim.x)
+
+// Sum of `n` floats of `p` in double, by the whole block, in an order fixed by (n, thread count).  Every thread gets the result.
+__device__ __forceinline__ double block_sum_partials(const float* __restrict__ p, int n, double* red) {
+    double s = 0.0;
+    for (int k = threadIdx.x; k < n; k += 256) s += (double)p[k];
+    __syncthreads();
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// ---- removal loss ------------------------------------------------------------------------------------------------------------------------------
+// Item q = elements [4q, 4q + 4) of ref's [B, chw]; its clean partner is pred row b, its shifted partner pred row B + b.
+template <bool VEC>
+__global__ __launch_bounds__(256) void removal_loss_kernel(const float* __restrict__ pred, const float* __restrict__ ref, float* __restrict__ dpred,
+                                                            float* __restrict__ partial, int B, int64_t chw, int64_t pbs, float cc, float cs) {
+    __shared__ float red[4];
+    const int64_t n = (int64_t)B * chw;
+    float sc = 0.f, ss = 0.f;
+    ITEM_STRIDE(q, (n + 3) >> 2) {
+        const int64_t f0 = q << 2;
+        if (VEC) {                                       // chw % 4 == 0: an item never straddles two rows
+            const int64_t b = f0 / chw, j = f0 - b * chw;
+            const f32x4 r = *reinterpret_cast<const f32x4*>(ref + f0);
+            const f32x4 pc = *reinterpret_cast<const f32x4*>(pred + b * pbs + j);
+            const f32x4 ps = *reinterpret_cast<const f32x4*>(pred + (b + B) * pbs + j);
+            f32x4 gc, gs;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float dc = pc[e] - r[e], ds = ps[e] - r[e];
+                sc += dc * dc;
+                ss += ds * ds;
+                gc[e] = cc * dc;
+                gs[e] = cs * ds;
+            }
+            *reinterpret_cast<f32x4*>(dpred + f0) = gc;
+            *reinterpret_cast<f32x4*>(dpred + n + f0) = gs;
+        } else {
+            for (int e = 0; e < 4; ++e) {
+                const int64_t f = f0 + e;
+                if (f >= n) break;
+                const int64_t b = f / chw, j = f - b * chw;
+                const float r = ref[f];
+                const float dc = pred[b * pbs + j] - r, ds = pred[(b + B) * pbs + j] - r;
+                sc += dc * dc;
+                ss += ds * ds;
+                dpred[f] = cc * dc;
+                dpred[n + f] = cs * ds;
+            }
+        }
+    }
+    sc = block_sum_256(sc, red);
+    ss = block_sum_256(ss, red);
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = sc;
+        partial[MAXP + blockIdx.x] = ss;
+    }
+}
+
+__global__ __launch_bounds__(256) void removal_loss_finish_kernel(const float* __restrict__ partial, int n_partial, double inv_n, float w_clean,
+                                                                   float w_shift, float* __restrict__ terms) {
+    __shared__ double red[256];
+    const double c = block_sum_partials(partial, n_partial, red);
+    const double s = block_sum_partials(partial + MAXP, n_partial, red);
+    if (threadIdx.x == 0) {
+        const float clean = (float)(c * inv_n), shift = (float)(s * inv_n);
+        terms[0] = w_clean * clean + w_shift * shift;
+        terms[1] = clean;
+        terms[2] = shift;
+    }
+}
+
+// ---- image-set statistics ----------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float post(float v, float mul, float add, float lo, float hi) {
+    return fminf(fmaxf(__fadd_rn(__fmul_rn(v, mul), add), lo), hi);      // postprocess_kernel's sequence
+}
+
+// Pass 1: mean_img[i] = mean over n of y[n][i], the sum in double.  A block owns 32 neighbouring positions; its 8 thread rows take every 8th image
+// each and their sums are added in row order.
+constexpr int MP = 32, MS = 8;
+__global__ __launch_bounds__(256) void image_set_mean_kernel(const float* __restrict__ x, float* __restrict__ mean_img, int N, int64_t chw,
+                                                              int64_t xbs, float mul, float add, float lo, float hi) {
+    __shared__ double red[MS][MP];
+    const int px = threadIdx.x % MP, sl = threadIdx.x / MP;
+    for (int64_t i0 = (int64_t)blockIdx.x * MP; i0 < chw; i0 += (int64_t)gridDim.x * MP) {
+        const int64_t i = i0 + px;
+        double s = 0.0;
+        if (i < chw)
+            for (int k = sl; k < N; k += MS) s += (double)post(x[(int64_t)k * xbs + i], mul, add, lo, hi);
+        __syncthreads();
+        red[sl][px] = s;
+        __syncthreads();
+        if (sl == 0 && i < chw) {
+            double t = red[0][px];
+#pragma unroll
+            for (int k = 1; k < MS; ++k) t += red[k][px];
+            mean_img[i] = (float)(t / (double)N);
+        }
+    }
+}
+
+// Pass 2: partial[block] = the block's share of sum_n ||y_n - mean||^2, partial[MAXP + block] = its share of sum_n TV(y_n).  An element adds its
+// squared deviation, then |down - y| (h + 1 < H), then |right - y| (w + 1 < W); VEC needs W % 4 == 0, so an item lies inside one image row.
+template <bool VEC>
+__global__ __launch_bounds__(256) void image_set_dev_tv_kernel(const float* __restrict__ x, const float* __restrict__ mean_img,
+                                                                float* __restrict__ partial, int N, int H, int W, int64_t chw, int64_t xbs,
+                                                                float mul, float add, float lo, float hi) {
+    __shared__ float red[4];
+    const int64_t n = (int64_t)N * chw;
+    float sq = 0.f, tv = 0.f;
+    ITEM_STRIDE(q, (n + 3) >> 2) {
+        const int64_t f0 = q << 2;
+        if (VEC) {
+            const int64_t img = f0 / chw, i = f0 - img * chw;
+            const int w0 = (int)(i % W), h = (int)((i / W) % H);
+            const float* row = x + img * xbs + i;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(row);
+            const f32x4 m = *reinterpret_cast<const f32x4*>(mean_img + i);
+            const bool down = h + 1 < H;
+            f32x4 dn = v;
+            if (down) dn = *reinterpret_cast<const f32x4*>(row + W);
+            const float nxt = (w0 + 4 < W) ? row[4] : 0.f;
+            float y[5];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) y[e] = post(v[e], mul, add, lo, hi);
+            y[4] = post(nxt, mul, add, lo, hi);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d = y[e] - m[e];
+                sq += d * d;
+                if (down) tv += fabsf(post(dn[e], mul, add, lo, hi) - y[e]);
+                if (w0 + e + 1 < W) tv += fabsf(y[e + 1] - y[e]);
+            }
+        } else {
+            for (int e = 0; e < 4; ++e) {
+                const int64_t f = f0 + e;
+                if (f >= n) break;
+                const int64_t img = f / chw, i = f - img * chw;
+                const int w = (int)(i % W), h = (int)((i / W) % H);
+                const float* p = x + img * xbs + i;
+                const float y = post(*p, mul, add, lo, hi);
+                const float d = y - mean_img[i];
+                sq += d * d;
+                if (h + 1 < H) tv += fabsf(post(p[W], mul, add, lo, hi) - y);
+                if (w + 1 < W) tv += fabsf(post(p[1], mul, add, lo, hi) - y);
+            }
+        }
+    }
+    sq = block_sum_256(sq, red);
+    tv = block_sum_256(tv, red);
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = sq;
+        partial[MAXP + blockIdx.x] = tv;
+    }
+}
+
+__global__ __launch_bounds__(256) void image_set_finish_kernel(const float* __restrict__ partial, int n_partial, float* __restrict__ stats) {
+    __shared__ double red[256];
+    const double a = block_sum_partials(partial, n_partial, red);
+    const double b = block_sum_partials(partial + MAXP, n_partial, red);
+    if (threadIdx.x == 0) {
+        stats[0] = (float)a;
+        stats[1] = (float)b;
+    }
+}
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" int vd_removal_loss(const float* pred, const float* ref, float w_clean, float w_shift, float gscale, float* dpred, float* terms,
+                               float* partial, int B, int64_t chw, int64_t pred_bstride, void* stream) {
+    VD_REQUIRE(pred && ref && dpred && terms && partial && B > 0 && chw > 0 && pred_bstride >= chw, "vd_removal_loss: bad args");
+    const int64_t n = (int64_t)B * chw;
+    const int grid = item_grid((n + 3) >> 2);
+    // gscale * w * 2 / n in double, rounded once: a power-of-two gscale scales dpred exactly
+    const float cc = (float)((double)gscale * (double)w_clean * 2.0 / (double)n);
+    const float cs = (float)((double)gscale * (double)w_shift * 2.0 / (double)n);
+    const bool vec = (chw % 4 == 0) && (pred_bstride % 4 == 0) && aligned16(pred) && aligned16(ref) && aligned16(dpred);
+    if (vec)
+        hipLaunchKernelGGL(removal_loss_kernel<true>, dim3(grid), dim3(256), 0, ST, pred, ref, dpred, partial, B, chw, pred_bstride, cc, cs);
+    else
+        hipLaunchKernelGGL(removal_loss_kernel<false>, dim3(grid), dim3(256), 0, ST, pred, ref, dpred, partial, B, chw, pred_bstride, cc, cs);
+    hipLaunchKernelGGL(removal_loss_finish_kernel, dim3(1), dim3(256), 0, ST, partial, grid, 1.0 / (double)n, w_clean, w_shift, terms);
+    VD_LAUNCH_CHECK("vd_removal_loss");
+    return 0;
+}
+
+extern "C" int vd_image_set_stats(const float* x, int N, int C, int H, int W, int64_t x_bstride, float mul, float add, float lo, float hi,
+                                  float* mean_img, float* stats, float* partial, void* stream) {
+    VD_REQUIRE(x && mean_img && stats && partial && N > 0 && C > 0 && H > 0 && W > 0, "vd_image_set_stats: bad args");
+    const int64_t chw = (int64_t)C * H * W;
+    VD_REQUIRE(x_bstride >= chw, "vd_image_set_stats: batch stride %lld < C*H*W %lld", (long long)x_bstride, (long long)chw);
+    const int mgrid = (int)((chw + MP - 1) / MP > 4096 ? 4096 : (chw + MP - 1) / MP);
+    hipLaunchKernelGGL(image_set_mean_kernel, dim3(mgrid), dim3(256), 0, ST, x, mean_img, N, chw, x_bstride, mul, add, lo, hi);
+    const int grid = item_grid(((int64_t)N * chw + 3) >> 2);
+    const bool vec = (W % 4 == 0) && (x_bstride % 4 == 0) && aligned16(x) && aligned16(mean_img);
+    if (vec)
+        hipLaunchKernelGGL(image_set_dev_tv_kernel<true>, dim3(grid), dim3(256), 0, ST, x, mean_img, partial, N, H, W, chw, x_bstride, mul, add,
+                           lo, hi);
+    else
+        hipLaunchKernelGGL(image_set_dev_tv_kernel<false>, dim3(grid), dim3(256), 0, ST, x, mean_img, partial, N, H, W, chw, x_bstride, mul, add,
+                           lo, hi);
+    hipLaunchKernelGGL(image_set_finish_kernel, dim3(1), dim3(256), 0, ST, partial, grid, stats);
+    VD_LAUNCH_CHECK("vd_image_set_stats");
+    return 0;
+}

@@ -7,8 +7,8 @@ preserves the shift, so the minimiser recovers (a multiple of) its trigger.  One
 (`UNet2DModel`'s input-gradient pass: frozen weights, dL/dsample only), one fused objective launch (`vd_trigger_inv_objective`), one column sum
 over the batch and the project's Adam kernel on `tau`.  Nothing here syncs with the host inside the loop.
 
-VP-type `UNet2DModel`s only (the latent UNet of the LDM configuration included: it is inverted in latent space, no VAE involved).  Classifying
-models from the inverted trigger (Elijah's uniformity / total-variation features) is left to the caller.
+VP-type `UNet2DModel`s only (the latent UNet of the LDM configuration included: it is inverted in latent space, no VAE involved).  What the
+inverted trigger is then used for -- Elijah's uniformity / total-variation features and the data-free removal fine-tune -- is in `mitigation`.
 """
 from __future__ import annotations
 

@@ -1054,6 +1054,32 @@ def trigger_inv_objective(e, tau, lam, loss, dout, dtau, partial):
     return loss
 
 
+def removal_loss(pred, ref, w_clean, w_shift, dpred, terms, partial, gscale=1.0):
+    """terms = {w_clean*clean + w_shift*shift, clean, shift} with clean = mse(pred[:B], ref), shift = mse(pred[B:], ref), and dpred = the
+    gradient of gscale * terms[0] with respect to pred, in one call (vd_removal_loss: fixed-order two-phase sum, bit-reproducible).
+    pred: [2B, C, H, W], may be a channel slice of a wider buffer; ref: [B, C, H, W] and dpred: [2B, C, H, W], contiguous."""
+    B2, Cc, H, W, pbs = _img(pred)
+    Bn, chw = B2 // 2, Cc * H * W
+    assert B2 == 2 * Bn and Bn >= 1 and tuple(ref.shape) == (Bn, Cc, H, W) and ref.is_contiguous() and ref.dtype == torch.float32
+    assert dpred.is_contiguous() and dpred.shape == pred.shape and dpred.dtype == torch.float32 and partial.numel() >= 2048 and terms.numel() >= 3
+    _timed("removal_loss (removal_loss_kernel + removal_loss_finish_kernel)", 4.0 * 5 * Bn * chw, "hbm", lambda: L.check(   # pred 2B, ref B read; dpred 2B written
+        _lib().vd_removal_loss(_p(pred), _p(ref), float(w_clean), float(w_shift), float(gscale), _p(dpred), _p(terms), _p(partial), Bn, chw, pbs,
+                               _s()), "vd_removal_loss"))
+    return terms
+
+
+def image_set_stats(x, mean_img, stats, partial, mul=0.5, add=0.5, lo=0.0, hi=1.0):
+    """mean_img = mean over N of y = clamp(x*mul + add, lo, hi) (ops.postprocess's values), stats = {sum_i ||y_i - mean_img||^2, sum_i TV(y_i)}
+    (vd_image_set_stats: two passes, fixed-order sums, bit-reproducible).  x: [N, C, H, W], may have a batch stride of its own."""
+    N, Cc, H, W, xbs = _img(x)
+    assert mean_img.is_contiguous() and tuple(mean_img.shape) == (Cc, H, W) and mean_img.dtype == torch.float32
+    assert stats.numel() >= 2 and stats.dtype == torch.float32 and partial.numel() >= 2048
+    _timed("image_set_stats (image_set_mean_kernel + image_set_dev_tv_kernel)", 4.0 * (2 * x.numel() + 2 * Cc * H * W), "hbm", lambda: L.check(   # x read by both passes
+        _lib().vd_image_set_stats(_p(x), N, Cc, H, W, xbs, float(mul), float(add), float(lo), float(hi), _p(mean_img), _p(stats), _p(partial),
+                                  _s()), "vd_image_set_stats"))
+    return stats
+
+
 def l2norm_sq(g, partial, out_sq):
     assert g.is_contiguous() and partial.numel() >= 1024
     _timed("l2norm_sq (sumsq_kernel)", 4.0 * g.numel(), "hbm",
