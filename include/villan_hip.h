@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats: additions only, no existing prototype moved */
+#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad: additions only */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -406,6 +406,14 @@ int vd_removal_loss(const float* pred, const float* ref, float w_clean, float w_
  * partial: >= 2048 floats.  Fixed-order sums (no atomics): bit-reproducible, and a strided view gives the bits of its contiguous copy. */
 int vd_image_set_stats(const float* x, int N, int C, int H, int W, int64_t x_bstride, float mul, float add, float lo, float hi,
                        float* mean_img, float* stats, float* partial, void* stream);
+/* Trigger-inversion objective of a score network (SDE-VE, defense_ve.py), in noise-prediction units: n[b] = -sigma * s[b],
+ * r = mean_b n[b] - lambda * tau, *loss = L = ||r||_2, dout[b] = sigma * dL/ds[b] = -sigma^2 r / (B L) for every b (contiguous [B, chw];
+ * pre-multiplied by sigma: the network is fed x = sigma * (eps + tau), so the sum over b of its input gradient for this dout is the chain term
+ * of dL/dtau) and dtau = -lambda r / L (the direct term).  s: [B, chw] with batch stride s_bstride >= chw; partial: >= 1024 floats.  The same
+ * two-phase fixed-order sum as vd_trigger_inv_objective: bit-reproducible, and a strided s gives the bits of its contiguous copy.  L == 0: zero
+ * gradients. */
+int vd_score_inv_objective(const float* s, const float* tau, float sigma, float lambda, float* loss, float* dout, float* dtau,
+                           float* partial, int B, int64_t chw, int64_t s_bstride, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K9 -- global grad-norm clip + Adam on flat buffers (VillanDiffusion.py:445,1165-1169).
@@ -447,6 +455,13 @@ int vd_vq_nearest(const float* z, const float* codebook, float* zq, int64_t* idx
  * vd_fourier_embedding: GaussianFourierProjection(log=True): emb[b] = [sin(log t_b W 2pi), cos(log t_b W 2pi)].
  * vd_rowscale: out[b][:] = x[b][:] * s[b] (divide=0) or / s[b] (divide=1)  (UNet2DModel's final `sample / timesteps`). */
 int vd_fir_resample2(const float* x, float* out, int64_t planes, int H, int W, int up, float scale, int accumulate, void* stream);
+/* Gradient of one level of NCSN++'s input-image pyramid with respect to its image (h = skip_conv(image) + ..., image_next = FIRdown(image)):
+ *   out[b][c][h][w] = sum_k w[k][c] * g[b][k][h][w]  +  0.25 * FIRup(coarse)[b][c][h][w] (coarse non-NULL)  (+ out, accumulate != 0)
+ * g: [B, K, H, W] with batch stride g_bstride >= K*H*W (a channel slice of a wider gradient is fine); w: [K, C], the 1x1 weight, C <= 4;
+ * coarse: the next level's gradient [B, C, H/2, W/2] or NULL; out: contiguous [B, C, H, W].  Exact f32, k summed in a fixed order, no
+ * atomics: bit-reproducible, and a strided g gives the bits of its contiguous copy.  The FIR taps are vd_fir_resample2's (up = 1). */
+int vd_pyramid_dgrad(const float* g, const float* w, const float* coarse, float* out, int B, int K, int C, int H, int W,
+                     int64_t g_bstride, int accumulate, void* stream);
 int vd_fourier_embedding(const float* t, const float* W, float* emb, int B, int half, void* stream);
 int vd_rowscale(const float* x, const float* s, float* out, int B, int64_t inner, int divide, void* stream);
 /* z ~ N(0,1) from Philox4x32-10 (throughput mode noise). */

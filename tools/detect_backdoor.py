@@ -4,7 +4,9 @@ villandiffusion_amd.mitigation):
 samples --n images from eps and --n from eps + trigger (the same eps) and writes detection.json (both feature sets, their ratios, the settings;
 a verdict only when --threshold is given: nothing here has been calibrated) and mean_shifted.pt (the mean shifted image, [C, H, W] in [0, 1]:
 for a collapsed set, the recovered target) into --out (default: the checkpoint directory).  Pixel-space UNet2DModel checkpoints (DDPM / DDIM /
-...); LDM and VE checkpoints are refused."""
+...) go to villandiffusion_amd.mitigation; a checkpoint whose network is an NCSNppModel (ScoreSdeVePipeline) goes to
+villandiffusion_amd.defense_ve: the sets start from sigma_T * eps and sigma_T * (eps + trigger), the record gains "sigma".  LDM and Karras-VE
+checkpoints are refused."""
 import argparse
 import json
 import os
@@ -26,16 +28,24 @@ def main(argv=None):
     args = ap.parse_args(argv)
 
     import torch
-    from villandiffusion_amd.mitigation import backdoor_features
+    from villandiffusion_amd.ncsnpp import NCSNppModel
     from villandiffusion_amd.pipelines import DiffusionPipeline
 
     pipe = DiffusionPipeline.from_pretrained(args.ckpt)
+    if isinstance(pipe.unet, NCSNppModel):
+        from villandiffusion_amd.defense_ve import backdoor_features
+        from villandiffusion_amd.pipelines import ScoreSdeVePipeline
+        pipe = ScoreSdeVePipeline(pipe.unet, pipe.scheduler)      # (from_pretrained hands back the base class: the predictor-corrector loop is this one's)
+    else:
+        from villandiffusion_amd.mitigation import backdoor_features
     tau = torch.load(args.trigger, map_location="cpu")
     res = backdoor_features(pipe, tau, n=args.n, batch=args.batch, num_inference_steps=args.steps, seed=args.seed)
     out = args.out or args.ckpt
     os.makedirs(out, exist_ok=True)
     torch.save(res.shifted.mean_image.detach().cpu(), os.path.join(out, "mean_shifted.pt"))
     info = {"ckpt": os.path.abspath(args.ckpt), "trigger": os.path.abspath(args.trigger), "pipeline": type(pipe).__name__} | res.as_dict()
+    if hasattr(res, "sigma"):
+        info["sigma"] = res.sigma
     if args.threshold is not None:
         info["threshold"] = args.threshold
         info["verdict"] = bool(res.verdict(args.threshold))

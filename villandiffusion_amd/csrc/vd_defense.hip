@@ -189,9 +189,63 @@ __global__ __launch_bounds__(256) void image_set_finish_kernel(const float* __re
     }
 }
 
+// ---- trigger-inversion objective of a score network (defense_ve.py) -----------------------------------------------------------------------------
+// The VE counterpart of vd_trigger_inv_objective, in noise-prediction units: n[b] = -sigma * s[b],  r = mean_b n[b] - lambda * tau,  L = ||r||_2.
+// Phase 1: r[i] (the batch sum in double: B is not bounded) parked in dtau, partial[block] = the block's sum of r^2.  Phase 2: every block adds the
+// partials in index order (the same value in every block and in every run), then dout[b][i] = sigma * dL/ds[b][i] = -sigma^2 r / (B L) for every
+// b and dtau[i] = -lambda r / L.  L = 0: zero gradients.
+__global__ __launch_bounds__(256) void score_inv_residual_kernel(const float* __restrict__ s, const float* __restrict__ tau, float* __restrict__ r,
+                                                                  float* __restrict__ partial, int B, int64_t n, int64_t s_bstride, float sigma,
+                                                                  float lambda) {
+    __shared__ float red[4];
+    float acc = 0.f;
+    ITEM_STRIDE(i, n) {
+        double m = 0.0;
+        for (int b = 0; b < B; ++b) m += (double)s[(int64_t)b * s_bstride + i];
+        const float v = (float)(-(double)sigma * m / (double)B) - lambda * tau[i];
+        r[i] = v;
+        acc += v * v;
+    }
+    acc = block_sum_256(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(256) void score_inv_grad_kernel(const float* __restrict__ partial, int n_partial, float* __restrict__ loss,
+                                                              float* __restrict__ dout, float* __restrict__ dtau, int B, int64_t n, float sigma,
+                                                              float lambda) {
+    __shared__ float Ls;
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int k = 0; k < n_partial; ++k) t += (double)partial[k];
+        Ls = (float)sqrt(t);
+    }
+    __syncthreads();
+    const float L = Ls;
+    const float inv = L > 0.f ? 1.0f / L : 0.f;
+    const float cb = -(sigma * sigma) * (inv / (float)B);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *loss = L;
+    ITEM_STRIDE(i, n) {
+        const float v = dtau[i];
+        const float gv = v * cb;
+        for (int b = 0; b < B; ++b) dout[(int64_t)b * n + i] = gv;
+        dtau[i] = -lambda * (v * inv);
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
+
+extern "C" int vd_score_inv_objective(const float* s, const float* tau, float sigma, float lambda, float* loss, float* dout, float* dtau,
+                                      float* partial, int B, int64_t chw, int64_t s_bstride, void* stream) {
+    VD_REQUIRE(s && tau && loss && dout && dtau && partial && B > 0 && chw > 0 && s_bstride >= chw, "vd_score_inv_objective: bad args");
+    VD_REQUIRE(sigma > 0.f, "vd_score_inv_objective: sigma must be positive, got %g", (double)sigma);
+    const int grid = item_grid(chw);
+    hipLaunchKernelGGL(score_inv_residual_kernel, dim3(grid), dim3(256), 0, ST, s, tau, dtau, partial, B, chw, s_bstride, sigma, lambda);
+    hipLaunchKernelGGL(score_inv_grad_kernel, dim3(grid), dim3(256), 0, ST, partial, grid, loss, dout, dtau, B, chw, sigma, lambda);
+    VD_LAUNCH_CHECK("vd_score_inv_objective");
+    return 0;
+}
 
 extern "C" int vd_removal_loss(const float* pred, const float* ref, float w_clean, float w_shift, float gscale, float* dpred, float* terms,
                                float* partial, int B, int64_t chw, int64_t pred_bstride, void* stream) {

@@ -737,6 +737,125 @@ extern "C" int vd_fir_resample2(const float* x, float* out, int64_t planes, int 
     return 0;
 }
 
+// ---- input-image pyramid of NCSN++: the gradient of one level with respect to its image (ncsnpp.py, record skip_conv_down) -----------------
+//   out[b][c][p] = sum_k w[k][c] * g[b][k][p]  +  0.25 * up(coarse)[b][c][p]  (+ out[b][c][p])
+// the transposed 1x1 convolution down to C <= 4 image channels fused with the adjoint of the FIR downsampling that made the next level (the up
+// kernel above, same taps, zero outside).  HBM-bound on g, read once: an ITEM is four consecutive pixels of one image (one f32x4 load per source
+// channel where pixels, stride and pointers allow, else four guarded scalar loads: which elements a thread owns and the order it adds them in
+// do not depend on that choice).  A block is 16 items x 16 slices of k: slice s adds k = s, s + 16, ... in increasing order, then the 16 slice
+// sums are added in slice order -- a fixed order, no atomics.  w waits in LDS, 512 source channels at a time.
+constexpr int PD_KS = 16, PD_IPB = 16, PD_WCHUNK = 512;
+template <int C>
+__global__ __launch_bounds__(256) void pyramid_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ w, const float* __restrict__ coarse,
+                                                            float* __restrict__ out, int B, int K, int H, int W, int64_t g_bstride, int accumulate,
+                                                            int vec) {
+    __shared__ float ws[PD_WCHUNK * C];
+    __shared__ float red[PD_KS][PD_IPB][C * 4];
+    const int HW = H * W, ipi = (HW + 3) >> 2;                 // items per image and channel
+    const int64_t items = (int64_t)B * ipi;
+    const int li = threadIdx.x % PD_IPB, s = threadIdx.x / PD_IPB;
+    const int64_t q = (int64_t)blockIdx.x * PD_IPB + li;
+    const bool live = q < items;
+    const int b = live ? (int)(q / ipi) : 0;
+    const int p0 = live ? (int)(q - (int64_t)b * ipi) * 4 : 0;
+    float acc[C][4];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[c][e] = 0.f;
+    const float* __restrict__ gp = g + (int64_t)b * g_bstride + p0;
+    for (int k0 = 0; k0 < K; k0 += PD_WCHUNK) {
+        const int kn = (K - k0 < PD_WCHUNK) ? K - k0 : PD_WCHUNK;
+        __syncthreads();
+        for (int i = threadIdx.x; i < kn * C; i += 256) ws[i] = w[(int64_t)k0 * C + i];
+        __syncthreads();
+        if (live) {
+#pragma unroll 4
+            for (int k = s; k < kn; k += PD_KS) {
+                const float* __restrict__ p = gp + (int64_t)(k0 + k) * HW;
+                float v[4];
+                if (vec) {
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = t[e];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (p0 + e < HW) ? p[e] : 0.f;
+                }
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const float wv = ws[k * C + c];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[c][e] += wv * v[e];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[s][li][c * 4 + e] = acc[c][e];
+    __syncthreads();
+    if ((int)threadIdx.x >= PD_IPB * C) return;
+    const int li2 = threadIdx.x / C, c = threadIdx.x - li2 * C;
+    const int64_t q2 = (int64_t)blockIdx.x * PD_IPB + li2;
+    if (q2 >= items) return;
+    const int b2 = (int)(q2 / ipi), pb = (int)(q2 - (int64_t)b2 * ipi) * 4;
+    float r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = red[0][li2][c * 4 + e];
+    for (int t = 1; t < PD_KS; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] += red[t][li2][c * 4 + e];
+    float* __restrict__ op = out + ((int64_t)b2 * C + c) * HW + pb;
+    const int CH = H >> 1, CW = W >> 1;
+    const float* __restrict__ xp = coarse ? coarse + ((int64_t)b2 * C + c) * CH * CW : nullptr;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int p = pb + e;
+        if (p >= HW) break;
+        float val = r[e];
+        if (xp) {                                             // fir_up2_kernel's value at (oy, ox), scale 1/4
+            const int oy = p / W, ox = p - oy * W;
+            const int ay = oy >> 1, ax = ox >> 1;
+            const int y0 = (oy & 1) ? ay : ay - 1, y1 = (oy & 1) ? ay + 1 : ay;
+            const float wy0 = (oy & 1) ? 0.75f : 0.25f, wy1 = (oy & 1) ? 0.25f : 0.75f;
+            const int x0 = (ox & 1) ? ax : ax - 1, x1 = (ox & 1) ? ax + 1 : ax;
+            const float wx0 = (ox & 1) ? 0.75f : 0.25f, wx1 = (ox & 1) ? 0.25f : 0.75f;
+            auto at = [&](int yy, int xx) -> float {
+                return ((unsigned)yy < (unsigned)CH && (unsigned)xx < (unsigned)CW) ? xp[yy * CW + xx] : 0.f;
+            };
+            const float u = wy0 * (wx0 * at(y0, x0) + wx1 * at(y0, x1)) + wy1 * (wx0 * at(y1, x0) + wx1 * at(y1, x1));
+            val += 0.25f * u;
+        }
+        op[e] = accumulate ? op[e] + val : val;
+    }
+}
+
+extern "C" int vd_pyramid_dgrad(const float* g, const float* w, const float* coarse, float* out, int B, int K, int C, int H, int W,
+                                int64_t g_bstride, int accumulate, void* stream) {
+    VD_REQUIRE(g && w && out && B > 0 && K > 0 && H > 0 && W > 0, "vd_pyramid_dgrad: bad args");
+    VD_REQUIRE(C >= 1 && C <= 4, "vd_pyramid_dgrad: %d image channels not in [1, 4]", C);
+    VD_REQUIRE(g_bstride >= (int64_t)K * H * W, "vd_pyramid_dgrad: batch stride %lld < K*H*W %lld", (long long)g_bstride, (long long)K * H * W);
+    VD_REQUIRE(!coarse || (H % 2 == 0 && W % 2 == 0), "vd_pyramid_dgrad: a coarser level needs even dims");
+    const int HW = H * W;
+    const int64_t items = (int64_t)B * ((HW + 3) >> 2);
+    const int64_t grid = (items + PD_IPB - 1) / PD_IPB;
+    VD_REQUIRE(grid <= 0x7fffffff, "vd_pyramid_dgrad: too many pixels");
+    const int vec = (HW % 4 == 0) && (g_bstride % 4 == 0) && ((((uintptr_t)g) & 15) == 0);
+#define PD_LAUNCH(CC) \
+    hipLaunchKernelGGL(pyramid_dgrad_kernel<CC>, dim3((unsigned)grid), dim3(256), 0, ST, g, w, coarse, out, B, K, H, W, g_bstride, accumulate, vec)
+    switch (C) {
+        case 1: PD_LAUNCH(1); break;
+        case 2: PD_LAUNCH(2); break;
+        case 3: PD_LAUNCH(3); break;
+        default: PD_LAUNCH(4); break;
+    }
+#undef PD_LAUNCH
+    VD_LAUNCH_CHECK("vd_pyramid_dgrad");
+    return 0;
+}
+
 extern "C" int vd_fourier_embedding(const float* t, const float* W, float* emb, int B, int half, void* stream) {
     VD_REQUIRE(t && W && emb && B > 0 && half > 0, "vd_fourier_embedding: bad args");
     hipLaunchKernelGGL(fourier_embedding_kernel, dim3((B * half + 255) / 256), dim3(256), 0, ST, t, W, emb, B, half);

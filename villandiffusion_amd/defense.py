@@ -9,6 +9,7 @@ over the batch and the project's Adam kernel on `tau`.  Nothing here syncs with 
 
 VP-type `UNet2DModel`s only (the latent UNet of the LDM configuration included: it is inverted in latent space, no VAE involved).  What the
 inverted trigger is then used for -- Elijah's uniformity / total-variation features and the data-free removal fine-tune -- is in `mitigation`.
+The same for the score network of SDE-VE (`NCSNppModel` with `ScoreSdeVeScheduler`) is `defense_ve`, a module of its own.
 """
 from __future__ import annotations
 

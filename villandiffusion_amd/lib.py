@@ -100,6 +100,7 @@ PROTOTYPES = {
     "vd_loss_fwd_bwd": (_i32, [_vp] * 6 + [_i32, _i64, _f32, _i32, _vp]),
     "vd_trigger_inv_objective": (_i32, [_vp, _vp, _f32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     "vd_removal_loss": (_i32, [_vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),
+    "vd_score_inv_objective": (_i32, [_vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     "vd_image_set_stats": (_i32, [_vp, _i32, _i32, _i32, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "vd_l2norm_sq": (_i32, [_vp, _i64, _vp, _vp, _vp]),
     "vd_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
@@ -109,6 +110,7 @@ PROTOTYPES = {
     "vd_ssim": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
     "vd_randn": (_i32, [_vp, _i64, C.c_uint64, C.c_uint64, _vp]),
     "vd_fir_resample2": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "vd_pyramid_dgrad": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp]),
     "vd_fourier_embedding": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "vd_rowscale": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _vp]),
     "vd_vq_nearest": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),

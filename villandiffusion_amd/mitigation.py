@@ -15,7 +15,7 @@
   training forward and backward at 2B, one `vd_removal_loss` launch pair (loss terms and dL/dpred in one read of pred) and the project's clip +
   Adam.  Nothing syncs with the host inside the loop.
 
-Pixel-space VP-type `UNet2DModel`s, single process.
+Pixel-space VP-type `UNet2DModel`s, single process.  (`NCSNppModel` / SDE-VE: `defense_ve`.)
 """
 from __future__ import annotations
 

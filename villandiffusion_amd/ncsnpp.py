@@ -11,6 +11,7 @@ C ABI wrapped in one ``autograd.Function``.  Skip concatenations are two strided
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from types import SimpleNamespace
 from typing import List, Optional, Tuple
@@ -85,20 +86,24 @@ class _ResnetPP:
         dsum = torch.empty_like(dout)
         ops.lincomb(dsum, [dout.contiguous()], [1.0 / self.scale])           # gradient wrt (shortcut + h)
         bias_ws = net.scratch_bc(B, self.cout)
-        ops.rowsum(dsum, bias_ws)
+        dx_only = net._dx_only                                                # input-gradient pass: no weight / bias / temb gradient launches
+        if not dx_only:
+            ops.rowsum(dsum, bias_ws)
         da2 = torch.empty_like(a2)
         self.conv2.bwd(dsum, a2, da2, bias_ws=bias_ws)
         dh1 = torch.empty_like(h1)
         self.norm2.bwd(da2, h1, m2, r2, dh1)
         dt = st.d_temb_all[:, self.temb_off:self.temb_off + self.cout]
-        ops.rowsum(dh1, dt, ws_ld=st.d_temb_all.stride(0))
+        if not dx_only:
+            ops.rowsum(dh1, dt, ws_ld=st.d_temb_all.stride(0))
         da1s = torch.empty_like(a1s)
         self.conv1.bwd(dh1, a1s, da1s, bias_ws=dt)
         # shortcut branch gradient wrt xs
         if self.has_sc:
             wsc = net.P[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin)
-            ops.conv_wgrad(dsum, xs, net.G[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin), B_PLAIN, net.wgrad_ws,
-                           accumulate=True, math_mode=_wgrad1x1_math(net, dsum, xs))
+            if not dx_only:
+                ops.conv_wgrad(dsum, xs, net.G[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin), B_PLAIN, net.wgrad_ws,
+                               accumulate=True, math_mode=_wgrad1x1_math(net, dsum, xs))
             net.colsum_later(bias_ws, net.G[self.prefix + ".conv_shortcut.bias"], B, self.cout)
             dxs = torch.empty_like(xs)
             HW = xs.shape[2] * xs.shape[3]
@@ -144,7 +149,9 @@ class _AttnPP:
 class NCSNppModel(UNet2DModel):
     """Drop-in for ``diffusers.UNet2DModel`` in its NCSN++ configuration (time_embedding_type='fourier', Skip blocks)."""
 
-    _input_grad = False                                       # its backward (below) yields parameter gradients only: no sample gradient, no input-gradient pass
+    # Off for the class: forward() and the autograd function treat the network as they always have (parameter gradients only, a frozen network
+    # takes the no-grad forward).  `with net.input_gradients():` switches THIS instance to UNet2DModel's four-case logic (defense_ve does).
+    _input_grad = False
 
     def __init__(self, in_channels=3, out_channels=3, sample_size=32, block_out_channels=(128, 256, 256, 256),
                  down_block_types=("SkipDownBlock2D", "AttnSkipDownBlock2D", "SkipDownBlock2D", "SkipDownBlock2D"),
@@ -231,6 +238,22 @@ class NCSNppModel(UNet2DModel):
         self._conv_out = _Conv(self, "conv_out", boc[0], out_channels)
         self._materialise()
         self.time_proj.weight.requires_grad_(False)          # GaussianFourierProjection.weight is a fixed random feature
+
+    @contextlib.contextmanager
+    def input_gradients(self):
+        """While open, forward() differentiates with respect to the sample too: a sample that requires grad gets its gradient from the backward
+        pass, and with every parameter frozen that pass is the input-gradient pass (_run_backward, weights=False).  Forward AND backward must run
+        inside.  The previous state comes back on exit, also after an exception; the class attribute is never written."""
+        had = "_input_grad" in self.__dict__
+        old = self.__dict__.get("_input_grad")
+        self._input_grad = True
+        try:
+            yield self
+        finally:
+            if had:
+                self._input_grad = old
+            else:
+                self.__dict__.pop("_input_grad", None)
 
     # ---- parameter plumbing differences ----
     def _decl(self, name, shape, fan_in=None, is_bias=False, ones=False, zeros=False, fourier=False):
@@ -348,13 +371,31 @@ class NCSNppModel(UNet2DModel):
             st.tape = None
         return out, st
 
-    def _run_backward(self, st, dout):
+    def _run_backward(self, st, dout, want_dx=False, weights=True):
+        """UNet2DModel._run_backward's contract.  weights: the parameter gradients, as ever.  want_dx: ALSO dL/dsample, the return value -- the
+        sample reaches the output through conv_in, through the input-image pyramid (skip_l = FIRdown(skip_{l-1}), h += skip_conv_l(skip_l)) and
+        through the final division by sigma (on the tape as rowscale); the pyramid's recurrence, deepest level first as the tape is popped, is
+        dS_l = W_l^T g_l + FIRup(dS_{l+1}) / 4 (one vd_pyramid_dgrad launch per level) and dx = conv_in's input gradient + FIRup(dS_1) / 4.
+        weights=False is the input-gradient pass of a frozen network: the same tape and main-stream kernels (the same dx, bit for bit), no weight
+        gradient, row or column sum, no time-embedding MLP backward; flat_grad, the side stream and bucket_ready_hook are never touched."""
+        if not weights:
+            if not want_dx:
+                return None
+            self._dx_only = True
+            try:
+                return self._backward_tape(st, dout, True, False)
+            finally:
+                self._dx_only = False
+        return self._backward_tape(st, dout, want_dx, True)
+
+    def _backward_tape(self, st, dout, want_dx, weights):
         dev = self._dev
         B = st.B
-        self._prepare_backward(B)
+        self._prepare_backward(B, weights)
         self._cs_begin(B)
         st.d_temb_all = self._d_temb_buffer(B)
-        hook = self.bucket_ready_hook
+        hook = self.bucket_ready_hook if weights else None
+        dx_in = dS = None                                      # dL/dsample; gradient wrt the current (deepest met so far) level of the input-image pyramid
         h_in, a, mo, ro, t, has_sk = st.out_saved
         dy = torch.empty_like(dout)
         ops.rowscale(dout.contiguous(), t, dy, divide=True)
@@ -403,16 +444,27 @@ class NCSNppModel(UNet2DModel):
             elif kind == "skip_conv_down":
                 _, blk, skimg = rec
                 # h = skip_conv(skimg) + h2: weight / bias gradients of the 1x1 conv; the image pyramid has no parameters upstream
-                ops.conv_wgrad(g, skimg, self.G[blk.skip_conv + ".weight"].view(blk.ch, -1), B_PLAIN, self.wgrad_ws, accumulate=True)
-                ws = self.scratch_bc(B, blk.ch)
-                ops.rowsum(g, ws)
-                self.colsum_later(ws, self.G[blk.skip_conv + ".bias"], B, blk.ch)
+                if weights:
+                    ops.conv_wgrad(g, skimg, self.G[blk.skip_conv + ".weight"].view(blk.ch, -1), B_PLAIN, self.wgrad_ws, accumulate=True)
+                    ws = self.scratch_bc(B, blk.ch)
+                    ops.rowsum(g, ws)
+                    self.colsum_later(ws, self.G[blk.skip_conv + ".bias"], B, blk.ch)
+                if want_dx:                                      # ... but the sample is: dS_l = W_l^T g + FIRup(dS_{l+1}) / 4
+                    nd = torch.empty_like(skimg)
+                    ops.pyramid_dgrad(g, self.P[blk.skip_conv + ".weight"].view(blk.ch, -1), nd, coarse=dS)
+                    dS = nd
             elif kind == "conv_in":
                 ops.add_strided(g, skip_grads.pop(), accumulate=True)
-                self._conv_in.bwd(g, rec[1], None)
+                if want_dx:
+                    dx_in = torch.empty_like(rec[1])
+                self._conv_in.bwd(g, rec[1], dx_in)
+                if want_dx and dS is not None:
+                    ops.fir_resample2(dS, dx_in, up=True, scale=0.25, accumulate=True)
             else:
                 raise RuntimeError(kind)
         assert not skip_grads
+        if not weights:
+            return dx_in
         if hook is not None:
             self._cs_flush()
             hook(2)
@@ -433,3 +485,4 @@ class NCSNppModel(UNet2DModel):
         self._cs_flush()
         if hook is not None:
             hook(3)
+        return dx_in

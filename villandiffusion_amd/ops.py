@@ -1054,6 +1054,20 @@ def trigger_inv_objective(e, tau, lam, loss, dout, dtau, partial):
     return loss
 
 
+def score_inv_objective(s, tau, sigma, lam, loss, dout, dtau, partial):
+    """The VE form of trigger_inv_objective, in noise-prediction units n[b] = -sigma * s[b]: loss = || mean_b n[b] - lam * tau ||_2,
+    dout[b] = sigma * dloss/ds[b] (every b) and dtau = the direct term -lam * r / loss (vd_score_inv_objective: fixed-order two-phase sum,
+    bit-reproducible; loss == 0 gives zero gradients).  s: [B, C, H, W], may have a batch stride of its own."""
+    Bn, Cc, H, W, sbs = _img(s)
+    chw = Cc * H * W
+    assert tau.is_contiguous() and tau.numel() == chw and dtau.is_contiguous() and dtau.numel() == chw and tau.dtype == dtau.dtype == torch.float32
+    assert dout.is_contiguous() and dout.shape == s.shape and dout.dtype == torch.float32 and partial.numel() >= 1024 and loss.numel() >= 1
+    _timed("score_inv_objective (score_inv_residual_kernel + score_inv_grad_kernel)", 4.0 * (2 * s.numel() + 3 * chw), "hbm", lambda: L.check(
+        _lib().vd_score_inv_objective(_p(s), _p(tau), float(sigma), float(lam), _p(loss), _p(dout), _p(dtau), _p(partial), Bn, chw, sbs, _s()),
+        "vd_score_inv_objective"))
+    return loss
+
+
 def removal_loss(pred, ref, w_clean, w_shift, dpred, terms, partial, gscale=1.0):
     """terms = {w_clean*clean + w_shift*shift, clean, shift} with clean = mse(pred[:B], ref), shift = mse(pred[B:], ref), and dpred = the
     gradient of gscale * terms[0] with respect to pred, in one call (vd_removal_loss: fixed-order two-phase sum, bit-reproducible).
@@ -1134,6 +1148,21 @@ def fir_resample2(x, out, up: bool, scale: float = 1.0, accumulate: bool = False
     assert x.is_contiguous() and out.is_contiguous()
     assert out.shape == ((Bn, Cc, 2 * H, 2 * W) if up else (Bn, Cc, H // 2, W // 2)), (x.shape, out.shape, up)
     L.check(_lib().vd_fir_resample2(_p(x), _p(out), Bn * Cc, H, W, int(up), scale, int(accumulate), _s()), "vd_fir_resample2")
+    return out
+
+
+def pyramid_dgrad(g, w, out, coarse=None, accumulate: bool = False):
+    """out = w^T g (+ fir_resample2(coarse, up=True) / 4) (+ out): the gradient of one level of NCSN++'s input-image pyramid with respect to its
+    image (vd_pyramid_dgrad).  g: [B, K, H, W], may be a channel slice of a wider buffer; w: [K, C] with C <= 4; coarse: [B, C, H/2, W/2] or None;
+    out: contiguous [B, C, H, W].  Exact f32 in a fixed order: bit-reproducible."""
+    Bn, K, H, W, gbs = _img(g)
+    Cc = w.shape[1]
+    assert w.is_contiguous() and tuple(w.shape) == (K, Cc) and w.dtype == torch.float32 and 1 <= Cc <= 4
+    assert out.is_contiguous() and tuple(out.shape) == (Bn, Cc, H, W) and out.dtype == torch.float32
+    assert coarse is None or (coarse.is_contiguous() and tuple(coarse.shape) == (Bn, Cc, H // 2, W // 2) and coarse.dtype == torch.float32
+                              and H % 2 == 0 and W % 2 == 0)
+    _timed("pyramid_dgrad (pyramid_dgrad_kernel)", 4.0 * (g.numel() + (2 + int(accumulate)) * out.numel()), "hbm", lambda: L.check(
+        _lib().vd_pyramid_dgrad(_p(g), _p(w), _p(coarse), _p(out), Bn, K, Cc, H, W, gbs, int(accumulate), _s()), "vd_pyramid_dgrad"))
     return out
 
 
