@@ -55,6 +55,23 @@ def test_frozen_flags_are_restored_after_an_exception():
     assert [p.requires_grad for p in net.parameters()] == flags and not flags[0] and all(flags[1:])
 
 
+def test_trainable_is_the_mirror_of_frozen_and_restores_after_an_exception():
+    from villandiffusion_amd import defense
+    net = _model()
+    params = list(net.parameters())
+    params[0].requires_grad_(False)                   # frozen by the caller: trainable inside, frozen again afterwards
+    params[2].requires_grad_(False)                   # in `skip`: never switched on
+    flags = [p.requires_grad for p in params]
+    with defense._trainable(net, skip=(params[2],)):
+        assert [p.requires_grad for p in params] == [i != 2 for i in range(len(params))]
+    assert [p.requires_grad for p in params] == flags
+    with pytest.raises(RuntimeError, match="boom"):
+        with defense._trainable(net, skip=(params[2],)):
+            assert all(p.requires_grad for i, p in enumerate(params) if i != 2) and not params[2].requires_grad
+            raise RuntimeError("boom")
+    assert [p.requires_grad for p in params] == flags and not flags[0] and not flags[2] and all(flags[3:]) and flags[1]
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="needs a box WITHOUT a GPU")
 def test_no_fallback_without_a_gpu():
     from villandiffusion_amd import defense, lib

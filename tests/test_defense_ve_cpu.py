@@ -41,6 +41,15 @@ def test_public_names_and_entry_points():
     assert callable(ops.score_inv_objective) and callable(ops.pyramid_dgrad)
 
 
+def test_shared_loops_and_checks_are_reused_not_copied():
+    from villandiffusion_amd import defense, defense_ve, mitigation
+    for name in ("_noise_of", "_check_loop_args", "_shape", "_trainable", "_objective_into", "_run_inversion"):
+        assert getattr(defense_ve, name) is getattr(defense, name), name
+    for name in ("_removal_step", "_run_removal", "_check_removal_args", "_check_feature_args"):
+        assert getattr(defense_ve, name) is getattr(mitigation, name), name
+    assert mitigation._noise_of is defense._noise_of
+
+
 def test_input_gradient_switch_is_per_instance():
     from villandiffusion_amd.ncsnpp import NCSNppModel
     a, b = _pp(), _pp()

@@ -38,6 +38,19 @@ def test_public_names():
     assert "mitigation" in defense.__doc__
 
 
+def test_shared_pieces_are_imported_and_a_vp_record_has_no_sigma():
+    from villandiffusion_amd import defense, mitigation
+    assert mitigation._noise_of is defense._noise_of and mitigation._trainable is defense._trainable
+    assert mitigation._check_loop_args is defense._check_loop_args and mitigation._shape is defense._shape
+    stats = mitigation.ImageSetStats(n=2, uniformity=1.0, tv=2.0, mean_image=torch.zeros(3, 4, 4))
+    f = mitigation.BackdoorFeatures(clean=stats, shifted=stats, uniformity_ratio=1.0, tv_ratio=1.0, n=2, batch=2, num_inference_steps=1, seed=0)
+    r = mitigation.BackdoorRemoval(total=[1.0], clean=[0.5], shift=[0.5], frozen=None, lr=1e-4, steps=1, batch=2, w_clean=1.0, w_shift=1.0,
+                                   max_grad_norm=1.0, timestep=999, seed=0)
+    assert f.sigma is None and r.sigma is None and "sigma" not in f.as_dict()
+    assert mitigation.BackdoorFeatures(clean=stats, shifted=stats, uniformity_ratio=1.0, tv_ratio=1.0, n=2, batch=2, num_inference_steps=1, seed=0,
+                                       sigma=380.0).sigma == 380.0
+
+
 def test_remove_backdoor_validates_before_touching_the_device(monkeypatch):
     from villandiffusion_amd import mitigation
     from villandiffusion_amd import schedulers as S

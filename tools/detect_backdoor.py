@@ -44,7 +44,7 @@ def main(argv=None):
     os.makedirs(out, exist_ok=True)
     torch.save(res.shifted.mean_image.detach().cpu(), os.path.join(out, "mean_shifted.pt"))
     info = {"ckpt": os.path.abspath(args.ckpt), "trigger": os.path.abspath(args.trigger), "pipeline": type(pipe).__name__} | res.as_dict()
-    if hasattr(res, "sigma"):
+    if res.sigma is not None:
         info["sigma"] = res.sigma
     if args.threshold is not None:
         info["threshold"] = args.threshold

@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from villandiffusion_amd import mitigation, ops  # noqa: E402
+from villandiffusion_amd.defense import _noise_of  # noqa: E402
 from villandiffusion_amd import schedulers as S  # noqa: E402
 from villandiffusion_amd.loss import LossFn  # noqa: E402
 from villandiffusion_amd.pipelines import sampler_forward  # noqa: E402
@@ -47,7 +48,7 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(0)
     shape = (3, 32, 32)
 
-    # ---- the removal step, as remove_backdoor runs it ----
+    # ---- the removal step, as remove_backdoor runs it: the two calls mitigation._run_removal makes per iteration ----
     net = UNet2DModel()
     net.reset_parameters(0)
     tau = torch.rand(shape, device="cuda", generator=gen)
@@ -58,14 +59,13 @@ def main():
     partial = torch.empty(2048, device="cuda")
     t2 = torch.full((2 * B,), 999.0, device="cuda")
     eps = torch.empty((B,) + shape, device="cuda")
+    per_iter = (eps.numel() + 3) // 4
     it = [0]
 
     def removal_step():
         it[0] += 1
-        ops.randn(eps, 0, it[0] * ((eps.numel() + 3) // 4))
-        mitigation._removal_into(net, teacher, tau, eps, t2, 1.0, 1.0, terms, partial)
-        opt.step()
-        net.zero_grad()
+        mitigation._removal_step(net, teacher, opt, tau, _noise_of("removal_step_ab", None, it[0] - 1, eps, 0, per_iter, "cuda"), t2, 1.0, 1.0,
+                                 terms, partial)
 
     # ---- the parts it is made of, as they existed: a training step at 2B and a sampler forward at B (a network of its own) ----
     net2 = UNet2DModel()

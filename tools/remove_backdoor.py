@@ -43,7 +43,7 @@ def main(argv=None):
     pipe.save_pretrained(args.out)
     info = {"ckpt": os.path.abspath(args.ckpt), "trigger": os.path.abspath(args.trigger), "steps": res.steps, "batch": res.batch, "lr": res.lr,
             "w_clean": res.w_clean, "w_shift": res.w_shift, "max_grad_norm": res.max_grad_norm, "seed": res.seed, "timestep": res.timestep,
-            "total": res.total, "clean": res.clean, "shift": res.shift} | ({"sigma": res.sigma} if hasattr(res, "sigma") else {})
+            "total": res.total, "clean": res.clean, "shift": res.shift} | ({"sigma": res.sigma} if res.sigma is not None else {})
     with open(os.path.join(args.out, "removal.json"), "w") as f:
         json.dump(info, f, indent=1)
     print(json.dumps({k: info[k] for k in ("steps", "batch", "lr", "timestep")} | {"shift_first": res.shift[0], "shift_last": res.shift[-1],

@@ -4,7 +4,8 @@
  * vd_pyramid_dgrad per level of the input-image pyramid against what it replaces -- one ops.gemm with M = 3 plus the ops.fir_resample2 launch
    that adds the coarser level's gradient -- in us, alternating, with the kernel's fraction of its HBM ceiling bytes(g) / 8 TB/s.  The kernel is
    kept only if it is not slower than the composed path in every alternation ("kernel_kept" per level and overall);
- * one VE inversion iteration and one VE removal step, ms (information only).
+ * one VE inversion iteration and one VE removal step, ms (information only): the calls the library's own loops make per iteration
+   (defense._noise_of, _objective_into and adam_update; mitigation._removal_step), not copies of them.
    python tools/ve_defense_ab.py [--alternations 3] [--batch 64] [--out profiles/r09_ve_defense_ab.json]
 Run it under a time limit of its own (`timeout -k 10 900 python tools/ve_defense_ab.py`)."""
 import argparse
@@ -28,7 +29,7 @@ def main():
     import torch
     from villandiffusion_amd import defense_ve, mitigation, ops
     from villandiffusion_amd import schedulers as S
-    from villandiffusion_amd.defense import _frozen, adam_update
+    from villandiffusion_amd.defense import _frozen, _noise_of, _objective_into, adam_update
     from villandiffusion_amd.lib import A_COL, B_PLAIN
     from villandiffusion_amd.ncsnpp import NCSNppModel
     from villandiffusion_amd.trainer import FusedAdam
@@ -118,13 +119,13 @@ def main():
     loss, partial = torch.empty(1, device="cuda"), torch.empty(2048, device="cuda")
     eps = torch.empty((Bi,) + shape, device="cuda")
     sig_i = torch.full((Bi,), sigma, device="cuda")
+    per_iter = (eps.numel() + 3) // 4
     it = [0]
 
-    def inversion_iteration():
+    def inversion_iteration():                               # one iteration of defense._run_inversion; the caller's context is opened here
         it[0] += 1
-        ops.randn(eps, 0, it[0] * ((eps.numel() + 3) // 4))
         with _frozen(net), net.input_gradients():
-            defense_ve._objective_into(net, tau, eps, sig_i, sigma, 0.5, loss, dtau, partial)
+            _objective_into(net, tau, _noise_of("ve_defense_ab", None, it[0] - 1, eps, 0, per_iter, "cuda"), sig_i, 0.5, loss, dtau, partial, sigma)
         adam_update(tau, dtau, m, v, it[0], 0.1)
 
     frozen = mitigation._frozen_copy(net)
@@ -134,12 +135,10 @@ def main():
     t2 = torch.full((2 * Bi,), sigma, device="cuda")
     tau_s = defense_ve._scaled(tau, sigma)
 
-    def removal_step():
+    def removal_step():                                      # one iteration of mitigation._run_removal as defense_ve.remove_backdoor calls it
         it[0] += 1
-        ops.randn(eps, 0, it[0] * ((eps.numel() + 3) // 4))
-        mitigation._removal_into(net, teacher, tau_s, defense_ve._scaled(eps, sigma), t2, sigma * sigma, sigma * sigma, terms, partial)
-        opt.step()
-        net.zero_grad()
+        eps_s = defense_ve._scaled(_noise_of("ve_defense_ab", None, it[0] - 1, eps, 0, per_iter, "cuda"), sigma)
+        mitigation._removal_step(net, teacher, opt, tau_s, eps_s, t2, sigma * sigma, sigma * sigma, terms, partial)
 
     info = {}
     for key, fn in (("inversion_iteration_ms", inversion_iteration), ("removal_step_ms", removal_step)):

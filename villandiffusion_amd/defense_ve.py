@@ -1,6 +1,8 @@
 """Trigger inversion, detection features and data-free removal (Elijah, An et al., AAAI 2024) for the score network of SDE-VE: `NCSNppModel`
-with `ScoreSdeVeScheduler`.  The same function names as `defense` / `mitigation`, which stay VP-only; the result types, the Adam update, the
-image-set statistics and the removal step are theirs, imported.
+with `ScoreSdeVeScheduler`.  The same function names as `defense` / `mitigation`, which stay VP-only; the result types, the shared argument
+checks, the objective launch sequence (`defense._objective_into` with a sigma), the inversion and removal loops, the Adam update and the image-set
+statistics are theirs, imported.  What is here is what SDE-VE alone needs: which model and scheduler are accepted, the noise level, the scaling by
+sigma, and a feature sampler that calls the pipeline once per chunk.
 
 Units.  The VE loss poisons in noise units: x_t = x_0 + sigma * eps + w * sigma * R, and -sigma * model(x_t, sigma) is trained towards
 eps + coef * R (loss.py).  So `tau` lives in noise units as well: the network is fed x = sigma * (eps + tau) at noise level sigma and its score
@@ -30,8 +32,10 @@ from typing import Callable, Optional, Union
 import torch
 
 from . import ops
-from .defense import TriggerInversion, _frozen, adam_update
-from .mitigation import BackdoorFeatures, BackdoorRemoval, _feature_inits, _frozen_copy, _ratio, _removal_into, image_set_stats
+from .defense import (TriggerInversion, _check_inversion_args, _check_loop_args, _check_pair, _check_trigger, _frozen, _noise_of,  # noqa: F401
+                      _objective_into, _run_inversion, _shape, _trainable, adam_update)
+from .mitigation import (BackdoorFeatures, BackdoorRemoval, _check_feature_args, _check_removal_args, _feature_inits, _features,  # noqa: F401
+                         _frozen_copy, _removal_into, _removal_step, _run_removal, image_set_stats)
 
 __all__ = ["inversion_objective", "invert_trigger", "backdoor_features", "removal_objective", "remove_backdoor"]
 
@@ -85,65 +89,14 @@ def _check_sigma(sigma, what: str) -> float:
     return sigma
 
 
-def _check_loop_args(what, model, steps, batch, lr, noise, shape):
-    if not isinstance(steps, int) or isinstance(steps, bool) or steps < 1:
-        raise ValueError(f"{what}: steps must be a positive int, got {steps!r}")
-    if not isinstance(batch, int) or isinstance(batch, bool) or batch < 1:
-        raise ValueError(f"{what}: batch must be a positive int, got {batch!r}")
-    if not (lr > 0.0 and lr != float("inf")):
-        raise ValueError(f"{what}: lr must be positive and finite, got {lr!r}")
-    if int(model.out_channels) != shape[0]:
-        raise ValueError(f"{what}: the objective compares the model's output with its input: out_channels {model.out_channels} != in_channels "
-                         f"{model.in_channels}")
-    if torch.is_tensor(noise) and tuple(noise.shape) != (steps, batch) + shape:
-        raise ValueError(f"{what}: noise must be [steps, batch, C, H, W] = {(steps, batch) + shape}, got {tuple(noise.shape)}")
-    if noise is not None and not torch.is_tensor(noise) and not callable(noise):
-        raise TypeError(f"{what}: noise is None, a tensor or a callable iteration -> [batch, C, H, W]")
-
-
-def _shape(model):
-    S = int(model.sample_size)
-    return (int(model.in_channels), S, S)
-
-
-def _noise_of(what, noise, it, eps_buf, seed, per_iter, dev):
-    if noise is None:
-        return ops.randn(eps_buf, int(seed), (it + 1) * per_iter)
-    eps = noise[it] if torch.is_tensor(noise) else noise(it)
-    if tuple(eps.shape) != tuple(eps_buf.shape):
-        raise ValueError(f"{what}: noise({it}) must be {tuple(eps_buf.shape)}, got {tuple(eps.shape)}")
-    return eps.detach().to(dev, torch.float32).contiguous()
-
-
 # ------------------------------------------------------------------------------------------------------------------------- inversion
-def _objective_into(model, tau, eps, sig, sigma, lam, loss, dtau, partial):
-    """One evaluation with caller-owned outputs: loss ([1] view) and dtau ([C, H, W]) are written in place.  The model must be frozen and its
-    input gradients switched on."""
-    B = eps.shape[0]
-    x = eps.clone()
-    ops.add_strided(x, tau.unsqueeze(0).expand_as(x), accumulate=True)
-    ops.scale_(x, sigma)                                                          # x[b] = sigma * (eps[b] + tau)
-    x.requires_grad_(True)
-    with torch.enable_grad():
-        s = model(x, sig)[0]
-    if s.grad_fn is None:
-        raise RuntimeError("trigger inversion: the model did not take its input-gradient pass (are its parameters frozen?)")
-    dout = torch.empty_like(s)
-    ops.score_inv_objective(s.detach(), tau, sigma, lam, loss, dout, dtau, partial)  # loss, sigma * dL/ds (every image), the direct term of dL/dtau
-    dx, = torch.autograd.grad(s, x, dout)
-    chw = tau.numel()
-    ops.colsum(dx.view(B, chw), dtau, B, chw, accumulate=True)                     # dtau = direct term + sum_b dL/dx[b] (dx/dtau = sigma is in dout)
-    return loss, dtau
-
-
 def inversion_objective(model, tau: torch.Tensor, eps: torch.Tensor, sigma, lam: float = 0.5):
     """(loss, dtau) of L(tau) = || mean_b -sigma * model(sigma * (eps[b] + tau), sigma) - lam * tau ||_2 at frozen weights: loss a [1] device
     tensor, dtau like tau.  sigma: one noise level (a float).  The parameters' requires_grad flags and the model's input-gradient switch are
     restored on exit."""
     _check_model(model, "inversion_objective")
     sigma = _check_sigma(sigma, "inversion_objective")
-    if eps.dim() != 4 or tuple(tau.shape) != tuple(eps.shape[1:]):
-        raise ValueError(f"inversion_objective: eps must be [B, C, H, W] and tau [C, H, W] (got {tuple(eps.shape)}, {tuple(tau.shape)})")
+    _check_pair("inversion_objective", tau, eps)
     from . import lib
     lib.require_device()
     dev = model.device
@@ -154,54 +107,28 @@ def inversion_objective(model, tau: torch.Tensor, eps: torch.Tensor, sigma, lam:
     partial = torch.empty(1024, device=dev, dtype=torch.float32)
     sig = torch.full((eps.shape[0],), sigma, device=dev, dtype=torch.float32)
     with _frozen(model), model.input_gradients():
-        _objective_into(model, tau, eps, sig, sigma, float(lam), loss, dtau, partial)
+        _objective_into(model, tau, eps, sig, float(lam), loss, dtau, partial, sigma)
     return loss, dtau
 
 
 def invert_trigger(model, noise_sched, *, steps: int, batch: int, lam: float = 0.5, lr: float = 0.1, seed: int = 0, timestep: Optional[int] = None,
                    init: Optional[torch.Tensor] = None,
                    noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None) -> TriggerInversion:
-    """Minimise the objective of the module docstring over `tau` with Adam(lr): the loop of `defense.invert_trigger`.
+    """Minimise the objective of the module docstring over `tau` with Adam(lr): `defense._run_inversion` at a sigma.
 
     noise_sched: a ScoreSdeVeScheduler (or a ScoreSdeVePipeline, for its scheduler).  timestep: index into the ascending training sigma table,
     default its last entry (sigma_T); the noise level used is recorded as `.extra["sigma"]`.  noise: None -- fresh per iteration from the device
     Philox stream (seed, disjoint counter ranges per iteration); a [steps, batch, C, H, W] tensor or a callable iteration -> [batch, C, H, W]
     of UNIT-variance noise makes a run reproducible against another implementation.  init: the starting trigger (default U[0, 1) from `seed`).
     lam: 0.5 for a backdoor trained with the sde solver, 1 for the ode solver."""
-    # ---- everything that can be checked without the device ----
-    lam, lr = float(lam), float(lr)
-    if not (lam == lam and abs(lam) != float("inf")):
-        raise ValueError(f"invert_trigger: lam must be finite, got {lam!r}")
+    # everything that can be checked is checked before the device is touched (in _run_inversion)
     _check_model(model, "invert_trigger")
     sched = _check_sched(noise_sched, "invert_trigger")
-    shape = _shape(model)
-    _check_loop_args("invert_trigger", model, steps, batch, lr, noise, shape)
+    shape, lam, lr = _check_inversion_args("invert_trigger", model, steps, batch, lam, lr, noise, init)
     T, sigma = _sigma_at(sched, timestep, "invert_trigger")
-    if init is not None and tuple(init.shape) != shape:
-        raise ValueError(f"invert_trigger: init must be {shape}, got {tuple(init.shape)}")
-
-    # ---- device state ----
-    from . import lib
-    lib.require_device()                                   # VillanHipError without an MI355X: there is no fallback
-    dev = model.device
-    if init is not None:
-        tau = init.detach().to(dev, torch.float32).contiguous().clone()
-    else:
-        tau = torch.rand(shape, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32).to(dev)
-    m, v = torch.zeros_like(tau), torch.zeros_like(tau)
-    dtau = torch.empty_like(tau)
-    losses = torch.zeros(steps, device=dev, dtype=torch.float32)
-    partial = torch.empty(1024, device=dev, dtype=torch.float32)
-    sig = torch.full((batch,), sigma, device=dev, dtype=torch.float32)
-    eps_buf = torch.empty((batch,) + shape, device=dev, dtype=torch.float32)
-    per_iter = (eps_buf.numel() + 3) // 4                  # Philox counters one iteration's noise consumes (four normals each)
     with _frozen(model), model.input_gradients():
-        for it in range(steps):
-            eps = _noise_of("invert_trigger", noise, it, eps_buf, seed, per_iter, dev)
-            _objective_into(model, tau, eps, sig, sigma, lam, losses[it:it + 1], dtau, partial)
-            adam_update(tau, dtau, m, v, it + 1, lr)
-    host = [float(x) for x in losses.cpu().tolist()]        # the one read of the loop's results
-    return TriggerInversion(trigger=tau, losses=host, lam=lam, lr=lr, steps=steps, batch=batch, timestep=T, seed=int(seed),
+        tau, losses = _run_inversion("invert_trigger", model, shape, sigma, lam, lr, steps, batch, seed, init, noise, sigma)
+    return TriggerInversion(trigger=tau, losses=losses, lam=lam, lr=lr, steps=steps, batch=batch, timestep=T, seed=int(seed),
                             extra={"sigma": sigma})
 
 
@@ -218,11 +145,6 @@ def backdoor_features(pipeline, trigger: torch.Tensor, *, n: int, batch: int, nu
     clamp(x, 0, 1), the images this pipeline returns.  For the call the scheduler draws its step noise from the device stream of `seed + 1` at
     offset 0, for both sets alike (they differ in the trigger alone); its own seed and offset are put back afterwards.
     Known: `ScoreSdeVeScheduler.step_correct` reads two norms on the host in every step; a sync-free corrector is out of scope here."""
-    for name, v in (("n", n), ("batch", batch)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-            raise ValueError(f"backdoor_features: {name} must be a positive int, got {v!r}")
-    if n < 2:
-        raise ValueError(f"backdoor_features: a pairwise statistic needs n >= 2 images, got {n}")
     from .pipelines import DiffusionPipeline, ScoreSdeVePipeline
     if not isinstance(pipeline, DiffusionPipeline):
         raise TypeError(f"backdoor_features needs a villandiffusion_amd pipeline, got {type(pipeline).__name__}")
@@ -231,12 +153,7 @@ def backdoor_features(pipeline, trigger: torch.Tensor, *, n: int, batch: int, nu
                                   f"to villandiffusion_amd.mitigation)")
     _check_model(pipeline.unet, "backdoor_features")
     sch = _check_sched(pipeline.scheduler, "backdoor_features")
-    shape = _shape(pipeline.unet)
-    if not torch.is_tensor(trigger) or tuple(trigger.shape) != shape:
-        raise ValueError(f"backdoor_features: trigger must be {shape}, got {tuple(trigger.shape) if torch.is_tensor(trigger) else type(trigger).__name__}")
-    steps = int(num_inference_steps) if num_inference_steps is not None else int(pipeline.default_steps)
-    if steps < 1:
-        raise ValueError(f"backdoor_features: num_inference_steps must be positive, got {steps}")
+    steps = _check_feature_args("backdoor_features", pipeline, trigger, n, batch, num_inference_steps)
     _, sigma = _sigma_at(sch, None, "backdoor_features")
 
     from . import lib
@@ -258,11 +175,7 @@ def backdoor_features(pipeline, trigger: torch.Tensor, *, n: int, batch: int, nu
             sets.append(_stats01(torch.cat(outs)))
     finally:
         sch.device_rng_seed, sch._rng_offset = seed0, off0
-    clean, shifted = sets
-    res = BackdoorFeatures(clean=clean, shifted=shifted, uniformity_ratio=_ratio(shifted.uniformity, clean.uniformity),
-                           tv_ratio=_ratio(shifted.tv, clean.tv), n=n, batch=batch, num_inference_steps=steps, seed=int(seed))
-    res.sigma = sigma                                       # (the VE records carry the noise level the sets start from)
-    return res
+    return _features(*sets, n, batch, steps, seed, sigma)                       # (the VE record carries the noise level the sets start from)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ removal
@@ -282,8 +195,7 @@ def removal_objective(model, frozen, tau: torch.Tensor, eps: torch.Tensor, sigma
     _check_model(model, "removal_objective")
     _check_model(frozen, "removal_objective")
     sigma = _check_sigma(sigma, "removal_objective")
-    if eps.dim() != 4 or tuple(tau.shape) != tuple(eps.shape[1:]):
-        raise ValueError(f"removal_objective: eps must be [B, C, H, W] and tau [C, H, W] (got {tuple(eps.shape)}, {tuple(tau.shape)})")
+    _check_pair("removal_objective", tau, eps)
     from . import lib
     lib.require_device()
     dev = model.device
@@ -305,55 +217,20 @@ def remove_backdoor(model, noise_sched, trigger: torch.Tensor, *, steps: int, ba
                     noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None) -> BackdoorRemoval:
     """Fine-tune `model` IN PLACE for `steps` Adam(lr, constant) iterations of the removal loss (noise-prediction units, see removal_objective)
     on `batch` unit-variance noise images each, at the noise level of `timestep` (default sigma_T), against a frozen copy of its state at entry
-    (returned as `.frozen`, never written).  The loop of `mitigation.remove_backdoor`: clip + FusedAdam, the three terms of every step read once
+    (returned as `.frozen`, never written).  The loop is `mitigation._run_removal`: clip + FusedAdam, the three terms of every step read once
     after the loop (clean / shift scaled by sigma^2 there).  `time_proj.weight`, the fixed Fourier features, is never unfrozen or written."""
-    # ---- everything that can be checked without the device ----
+    # everything that can be checked is checked before the device is touched (in _run_removal)
     lr, w_clean, w_shift = float(lr), float(w_clean), float(w_shift)
-    for name, w in (("w_clean", w_clean), ("w_shift", w_shift)):
-        if not (w >= 0.0 and w != float("inf")):
-            raise ValueError(f"remove_backdoor: {name} must be finite and non-negative, got {w!r}")
-    if max_grad_norm is not None and not (float(max_grad_norm) > 0.0 and math.isfinite(float(max_grad_norm))):
-        raise ValueError(f"remove_backdoor: max_grad_norm must be positive and finite (or None: no clipping), got {max_grad_norm!r}")
+    _check_removal_args("remove_backdoor", w_clean, w_shift, max_grad_norm)
     _check_model(model, "remove_backdoor")
     sched = _check_sched(noise_sched, "remove_backdoor")
     shape = _shape(model)
     _check_loop_args("remove_backdoor", model, steps, batch, lr, noise, shape)
     T, sigma = _sigma_at(sched, timestep, "remove_backdoor")
-    if not torch.is_tensor(trigger) or tuple(trigger.shape) != shape:
-        raise ValueError(f"remove_backdoor: trigger must be {shape}, got {tuple(trigger.shape) if torch.is_tensor(trigger) else type(trigger).__name__}")
-
-    # ---- device state ----
-    from . import lib
-    from .trainer import FusedAdam
-    lib.require_device()                                   # VillanHipError without an MI355X: there is no fallback
-    dev = model.device
-    tau_s = _scaled(trigger.detach().to(dev, torch.float32).contiguous(), sigma)
-    frozen = _frozen_copy(model)
-    opt = FusedAdam(model, lr, max_grad_norm=None if max_grad_norm is None else float(max_grad_norm))
-    curves = torch.zeros((steps, 3), device=dev, dtype=torch.float32)
-    partial = torch.empty(2048, device=dev, dtype=torch.float32)
-    t2 = torch.full((2 * batch,), sigma, device=dev, dtype=torch.float32)
-    eps_buf = torch.empty((batch,) + shape, device=dev, dtype=torch.float32)
-    per_iter = (eps_buf.numel() + 3) // 4
+    _check_trigger("remove_backdoor", trigger, shape)
     s2 = sigma * sigma
-    teacher = _teacher(frozen)
-    fixed = model.time_proj.weight
-    flags = [(p, p.requires_grad) for p in model.parameters()]
-    try:
-        for p, _ in flags:
-            if p is not fixed:
-                p.requires_grad_(True)                     # the fine-tune trains every parameter but the Fourier features; the caller's flags come back below
-        model.zero_grad()
-        for it in range(steps):
-            eps = _noise_of("remove_backdoor", noise, it, eps_buf, seed, per_iter, dev)
-            _removal_into(model, teacher, tau_s, _scaled(eps, sigma), t2, w_clean * s2, w_shift * s2, curves[it], partial)
-            opt.step()
-            model.zero_grad()
-    finally:
-        for p, f in flags:
-            p.requires_grad_(f)
-    host = curves.cpu().tolist()                            # the one read of the loop's results
-    res = BackdoorRemoval(total=[r[0] for r in host], clean=[r[1] * s2 for r in host], shift=[r[2] * s2 for r in host], frozen=frozen, lr=lr,
-                          steps=steps, batch=batch, w_clean=w_clean, w_shift=w_shift, max_grad_norm=max_grad_norm, timestep=T, seed=int(seed))
-    res.sigma = sigma                                       # (the VE records carry the noise level of the fine-tune)
-    return res
+    frozen, host = _run_removal("remove_backdoor", model, _teacher, trigger, shape, sigma, w_clean * s2, w_shift * s2, lr, max_grad_norm, steps,
+                                batch, seed, noise, prepare=lambda x: _scaled(x, sigma), skip=(model.time_proj.weight,))
+    return BackdoorRemoval(total=[r[0] for r in host], clean=[r[1] * s2 for r in host], shift=[r[2] * s2 for r in host], frozen=frozen, lr=lr,
+                           steps=steps, batch=batch, w_clean=w_clean, w_shift=w_shift, max_grad_norm=max_grad_norm, timestep=T, seed=int(seed),
+                           sigma=sigma)                    # (the VE record carries the noise level of the fine-tune)

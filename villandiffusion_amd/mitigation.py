@@ -15,7 +15,8 @@
   training forward and backward at 2B, one `vd_removal_loss` launch pair (loss terms and dL/dpred in one read of pred) and the project's clip +
   Adam.  Nothing syncs with the host inside the loop.
 
-Pixel-space VP-type `UNet2DModel`s, single process.  (`NCSNppModel` / SDE-VE: `defense_ve`.)
+Pixel-space VP-type `UNet2DModel`s, single process.  (`NCSNppModel` / SDE-VE: `defense_ve`, which imports from here what the two families
+share: `_check_feature_args`, `_features`, `_check_removal_args`, `_removal_step` and the removal loop `_run_removal`.)
 """
 from __future__ import annotations
 
@@ -26,7 +27,8 @@ from typing import Callable, List, Optional, Union
 import torch
 
 from . import ops
-from .defense import _check_model, _frozen
+from .defense import (_check_count, _check_loop_args, _check_model, _check_pair, _check_trigger, _frozen, _noise_of, _shape, _trainable,
+                      _vp_timestep)
 
 __all__ = ["ImageSetStats", "image_set_stats", "BackdoorFeatures", "backdoor_features", "removal_objective", "BackdoorRemoval", "remove_backdoor"]
 
@@ -76,6 +78,7 @@ class BackdoorFeatures:
     batch: int
     num_inference_steps: int
     seed: int
+    sigma: Optional[float] = None          # SDE-VE (`defense_ve`) only: the noise level the sets start from
 
     def verdict(self, threshold: float) -> bool:
         """True (backdoored) when the shifted set is more than 1/threshold times as alike as the clean one.  The threshold is the caller's:
@@ -101,11 +104,28 @@ def _check_pipeline(pipeline):
                                   f"pipelines only")
 
 
+def _check_feature_args(what, pipeline, trigger, n, batch, num_inference_steps) -> int:
+    """The checks both `backdoor_features` share, after the family's own check of the pipeline.  -> the resolved step count"""
+    _check_count(what, "n", n)
+    _check_count(what, "batch", batch)
+    if n < 2:
+        raise ValueError(f"{what}: a pairwise statistic needs n >= 2 images, got {n}")
+    _check_trigger(what, trigger, _shape(pipeline.unet))
+    steps = int(num_inference_steps) if num_inference_steps is not None else int(pipeline.default_steps)
+    if steps < 1:
+        raise ValueError(f"{what}: num_inference_steps must be positive, got {steps}")
+    return steps
+
+
+def _features(clean: ImageSetStats, shifted: ImageSetStats, n, batch, steps, seed, sigma=None) -> BackdoorFeatures:
+    return BackdoorFeatures(clean=clean, shifted=shifted, uniformity_ratio=_ratio(shifted.uniformity, clean.uniformity),
+                            tv_ratio=_ratio(shifted.tv, clean.tv), n=n, batch=batch, num_inference_steps=steps, seed=int(seed), sigma=sigma)
+
+
 def _feature_inits(pipeline, n: int, batch: int, seed: int) -> List[torch.Tensor]:
     """The n noise images of `backdoor_features` as chunks of at most `batch`: chunk k is drawn from the device Philox stream of `seed` at
     counter offset k * ceil(batch*C*H*W / 4), so the chunks are disjoint and a chunk does not depend on n."""
-    u = pipeline.unet
-    shape = (int(u.in_channels), int(u.sample_size), int(u.sample_size))
+    shape = _shape(pipeline.unet)
     per_chunk = (batch * shape[0] * shape[1] * shape[2] + 3) // 4
     out = []
     for k, first in enumerate(range(0, n, batch)):
@@ -130,19 +150,9 @@ def backdoor_features(pipeline, trigger: torch.Tensor, *, n: int, batch: int, nu
     The inits come from the Philox stream of `seed`; a scheduler that draws its step noise on the device and has no `device_rng_seed` gets
     `seed + 1` for the call, so the two never share counters.  Both sets are sampled from the same scheduler offset: they differ in the trigger
     alone."""
-    for name, v in (("n", n), ("batch", batch)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-            raise ValueError(f"backdoor_features: {name} must be a positive int, got {v!r}")
-    if n < 2:
-        raise ValueError(f"backdoor_features: a pairwise statistic needs n >= 2 images, got {n}")
     _check_pipeline(pipeline)
-    u, sch = pipeline.unet, pipeline.scheduler
-    shape = (int(u.in_channels), int(u.sample_size), int(u.sample_size))
-    if not torch.is_tensor(trigger) or tuple(trigger.shape) != shape:
-        raise ValueError(f"backdoor_features: trigger must be {shape}, got {tuple(trigger.shape) if torch.is_tensor(trigger) else type(trigger).__name__}")
-    steps = int(num_inference_steps) if num_inference_steps is not None else int(pipeline.default_steps)
-    if steps < 1:
-        raise ValueError(f"backdoor_features: num_inference_steps must be positive, got {steps}")
+    steps = _check_feature_args("backdoor_features", pipeline, trigger, n, batch, num_inference_steps)
+    sch = pipeline.scheduler
 
     from . import lib
     lib.require_device()
@@ -165,8 +175,7 @@ def backdoor_features(pipeline, trigger: torch.Tensor, *, n: int, batch: int, nu
             sch.device_rng_seed = None
             if off0 is not None:
                 sch._rng_offset = off0
-    return BackdoorFeatures(clean=clean, shifted=shifted, uniformity_ratio=_ratio(shifted.uniformity, clean.uniformity),
-                            tv_ratio=_ratio(shifted.tv, clean.tv), n=n, batch=batch, num_inference_steps=steps, seed=int(seed))
+    return _features(clean, shifted, n, batch, steps, seed)
 
 
 def _ratio(a: float, b: float) -> float:
@@ -188,6 +197,7 @@ class BackdoorRemoval:
     max_grad_norm: Optional[float]
     timestep: int
     seed: int
+    sigma: Optional[float] = None          # SDE-VE (`defense_ve`) only: the noise level of the fine-tune
 
 
 def _frozen_copy(model):
@@ -224,6 +234,53 @@ def _removal_into(model, teacher, tau, eps, t2, w_clean, w_shift, terms, partial
     return terms
 
 
+def _removal_step(model, teacher, opt, tau, eps, t2, w_clean, w_shift, terms, partial):
+    """One step of `remove_backdoor`'s loop: the evaluation into `terms`, clip + Adam, the gradient reset."""
+    _removal_into(model, teacher, tau, eps, t2, w_clean, w_shift, terms, partial)
+    opt.step()
+    model.zero_grad()
+
+
+def _check_removal_args(what, w_clean, w_shift, max_grad_norm):
+    for name, w in (("w_clean", w_clean), ("w_shift", w_shift)):
+        if not (w >= 0.0 and w != float("inf")):
+            raise ValueError(f"{what}: {name} must be finite and non-negative, got {w!r}")
+    if max_grad_norm is not None and not (float(max_grad_norm) > 0.0 and math.isfinite(float(max_grad_norm))):
+        raise ValueError(f"{what}: max_grad_norm must be positive and finite (or None: no clipping), got {max_grad_norm!r}")
+
+
+def _check_f16(what, model):
+    if getattr(model, "conv_math", None) == "f16":
+        raise NotImplementedError(f"{what}: conv_math 'f16' needs loss scaling, which the removal loop does not have; use 'bf16x3', 'f32' or 'bf16'")
+
+
+def _run_removal(what, model, make_teacher, trigger, shape, t, w_clean, w_shift, lr, max_grad_norm, steps, batch, seed, noise,
+                 prepare=lambda x: x, skip=()):
+    """The removal loop of both families: `steps` iterations of clip + FusedAdam(lr) on `model`, in place, at the noise level `t`, against a
+    frozen copy of its state at entry.  make_teacher: frozen copy -> (x, t -> its output), called once before the loop with the model's
+    parameters already trainable.  prepare: what turns the trigger and each iteration's unit noise into network input units (SDE-VE scales by
+    sigma).  skip: parameters that are never unfrozen.  -> (the frozen copy, the [total, clean, shift] rows of every step, on the host)"""
+    from . import lib
+    from .trainer import FusedAdam
+    lib.require_device()                                   # VillanHipError without an MI355X: there is no fallback
+    dev = model.device
+    tau = prepare(trigger.detach().to(dev, torch.float32).contiguous())
+    frozen = _frozen_copy(model)
+    opt = FusedAdam(model, lr, max_grad_norm=None if max_grad_norm is None else float(max_grad_norm))
+    curves = torch.zeros((steps, 3), device=dev, dtype=torch.float32)
+    partial = torch.empty(2048, device=dev, dtype=torch.float32)
+    t2 = torch.full((2 * batch,), float(t), device=dev, dtype=torch.float32)
+    eps_buf = torch.empty((batch,) + shape, device=dev, dtype=torch.float32)
+    per_iter = (eps_buf.numel() + 3) // 4                  # Philox counters one iteration's noise consumes (four normals each)
+    with _trainable(model, skip):                          # the fine-tune trains every parameter (but `skip`); the caller's flags come back on exit
+        teacher = make_teacher(frozen)                     # before the loop: a captured forward synchronises
+        model.zero_grad()
+        for it in range(steps):
+            eps = prepare(_noise_of(what, noise, it, eps_buf, seed, per_iter, dev))
+            _removal_step(model, teacher, opt, tau, eps, t2, w_clean, w_shift, curves[it], partial)
+    return frozen, curves.cpu().tolist()                   # the one read of the loop's results
+
+
 def _timesteps(t, B2, dev):
     if torch.is_tensor(t):
         t = t.to(dev).reshape(-1)
@@ -241,10 +298,8 @@ def removal_objective(model, frozen, tau: torch.Tensor, eps: torch.Tensor, t, w_
     gradient of this evaluation alone).  For tests and for callers with an optimiser of their own."""
     _check_model(model)
     _check_model(frozen)
-    if eps.dim() != 4 or tuple(tau.shape) != tuple(eps.shape[1:]):
-        raise ValueError(f"removal_objective: eps must be [B, C, H, W] and tau [C, H, W] (got {tuple(eps.shape)}, {tuple(tau.shape)})")
-    if getattr(model, "conv_math", None) == "f16":
-        raise NotImplementedError("removal_objective: conv_math 'f16' needs loss scaling, which the removal loop does not have; use 'bf16x3', 'f32' or 'bf16'")
+    _check_pair("removal_objective", tau, eps)
+    _check_f16("removal_objective", model)
     from . import lib
     from .pipelines import sampler_forward
     lib.require_device()
@@ -270,73 +325,17 @@ def remove_backdoor(model, noise_sched, trigger: torch.Tensor, *, steps: int, ba
     timestep: defaults to the scheduler's last training timestep.  noise: None -- fresh per iteration from the device Philox stream (seed, disjoint
     counter ranges per iteration); a [steps, batch, C, H, W] tensor or a callable iteration -> [batch, C, H, W] makes a run reproducible against
     another implementation.  The three loss terms of every step stay on the device until the loop is over."""
-    # ---- everything that can be checked without the device ----
-    if not isinstance(steps, int) or isinstance(steps, bool) or steps < 1:
-        raise ValueError(f"remove_backdoor: steps must be a positive int, got {steps!r}")
-    if not isinstance(batch, int) or isinstance(batch, bool) or batch < 1:
-        raise ValueError(f"remove_backdoor: batch must be a positive int, got {batch!r}")
+    # everything that can be checked is checked before the device is touched (in _run_removal)
     lr, w_clean, w_shift = float(lr), float(w_clean), float(w_shift)
-    if not (lr > 0.0 and lr != float("inf")):
-        raise ValueError(f"remove_backdoor: lr must be positive and finite, got {lr!r}")
-    for name, w in (("w_clean", w_clean), ("w_shift", w_shift)):
-        if not (w >= 0.0 and w != float("inf")):
-            raise ValueError(f"remove_backdoor: {name} must be finite and non-negative, got {w!r}")
-    if max_grad_norm is not None and not (float(max_grad_norm) > 0.0 and math.isfinite(float(max_grad_norm))):
-        raise ValueError(f"remove_backdoor: max_grad_norm must be positive and finite (or None: no clipping), got {max_grad_norm!r}")
+    _check_removal_args("remove_backdoor", w_clean, w_shift, max_grad_norm)
     _check_model(model, noise_sched)
-    if getattr(model, "conv_math", None) == "f16":
-        raise NotImplementedError("remove_backdoor: conv_math 'f16' needs loss scaling, which the removal loop does not have; use 'bf16x3', 'f32' or 'bf16'")
-    T_train = int(noise_sched.config.num_train_timesteps)
-    T = T_train - 1 if timestep is None else int(timestep)
-    if not 0 <= T < T_train:
-        raise ValueError(f"remove_backdoor: timestep {T} outside the scheduler's [0, {T_train})")
-    S = int(model.sample_size)
-    shape = (int(model.in_channels), S, S)
-    if int(model.out_channels) != shape[0]:
-        raise ValueError(f"remove_backdoor: the loss compares outputs on a shifted input: out_channels {model.out_channels} != in_channels "
-                         f"{model.in_channels}")
-    if not torch.is_tensor(trigger) or tuple(trigger.shape) != shape:
-        raise ValueError(f"remove_backdoor: trigger must be {shape}, got {tuple(trigger.shape) if torch.is_tensor(trigger) else type(trigger).__name__}")
-    if torch.is_tensor(noise) and tuple(noise.shape) != (steps, batch) + shape:
-        raise ValueError(f"remove_backdoor: noise must be [steps, batch, C, H, W] = {(steps, batch) + shape}, got {tuple(noise.shape)}")
-    if noise is not None and not torch.is_tensor(noise) and not callable(noise):
-        raise TypeError("remove_backdoor: noise is None, a tensor or a callable iteration -> [batch, C, H, W]")
-
-    # ---- device state ----
-    from . import lib
+    _check_f16("remove_backdoor", model)
+    shape = _shape(model)
+    _check_loop_args("remove_backdoor", model, steps, batch, lr, noise, shape)
+    T = _vp_timestep("remove_backdoor", noise_sched, timestep)
+    _check_trigger("remove_backdoor", trigger, shape)
     from .pipelines import sampler_forward
-    from .trainer import FusedAdam
-    lib.require_device()                                   # VillanHipError without an MI355X: there is no fallback
-    dev = model.device
-    tau = trigger.detach().to(dev, torch.float32).contiguous()
-    frozen = _frozen_copy(model)
-    opt = FusedAdam(model, lr, max_grad_norm=None if max_grad_norm is None else float(max_grad_norm))
-    curves = torch.zeros((steps, 3), device=dev, dtype=torch.float32)
-    partial = torch.empty(2048, device=dev, dtype=torch.float32)
-    t2 = torch.full((2 * batch,), float(T), device=dev, dtype=torch.float32)
-    eps_buf = torch.empty((batch,) + shape, device=dev, dtype=torch.float32)
-    per_iter = (eps_buf.numel() + 3) // 4                  # Philox counters one iteration's noise consumes (four normals each)
-    flags = [(p, p.requires_grad) for p in model.parameters()]
-    try:
-        for p, _ in flags:
-            p.requires_grad_(True)                         # the fine-tune trains every parameter; the caller's flags come back below
-        teacher = sampler_forward(frozen, batch)           # captured once, before the loop (the capture synchronises)
-        model.zero_grad()
-        for it in range(steps):
-            if noise is None:
-                ops.randn(eps_buf, int(seed), (it + 1) * per_iter)
-                eps = eps_buf
-            else:
-                eps = noise[it] if torch.is_tensor(noise) else noise(it)
-                if tuple(eps.shape) != (batch,) + shape:
-                    raise ValueError(f"remove_backdoor: noise({it}) must be {(batch,) + shape}, got {tuple(eps.shape)}")
-                eps = eps.detach().to(dev, torch.float32).contiguous()
-            _removal_into(model, teacher, tau, eps, t2, w_clean, w_shift, curves[it], partial)
-            opt.step()
-            model.zero_grad()
-    finally:
-        for p, f in flags:
-            p.requires_grad_(f)
-    host = curves.cpu().tolist()                            # the one read of the loop's results
+    frozen, host = _run_removal("remove_backdoor", model, lambda twin: sampler_forward(twin, batch), trigger, shape, T, w_clean, w_shift, lr,
+                                max_grad_norm, steps, batch, seed, noise)
     return BackdoorRemoval(total=[r[0] for r in host], clean=[r[1] for r in host], shift=[r[2] for r in host], frozen=frozen, lr=lr, steps=steps,
                            batch=batch, w_clean=w_clean, w_shift=w_shift, max_grad_norm=max_grad_norm, timestep=T, seed=int(seed))
