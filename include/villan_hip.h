@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad: additions only */
+#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge: additions only */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -414,6 +414,14 @@ int vd_image_set_stats(const float* x, int N, int C, int H, int W, int64_t x_bst
  * gradients. */
 int vd_score_inv_objective(const float* s, const float* tau, float sigma, float lambda, float* loss, float* dout, float* dtau,
                            float* partial, int B, int64_t chw, int64_t s_bstride, void* stream);
+/* Streaming form of vd_image_set_stats (defense_ldm.py): merges the result (mean_b, stats_b) of a chunk of n_b images into the running result
+ * (mean_a, stats_a) of n_a images by the pairwise update of Chan et al. -- never the sum / sum-of-squares form.  With delta = mean_b - mean_a and
+ * n = n_a + n_b:  mean_a += delta * n_b / n  (in double, rounded once);  stats_a[0] += stats_b[0] + n_a*n_b/n * sum(delta^2);
+ * stats_a[1] += stats_b[1].  n_a == 0 copies b into a.  mean_*: [chw] f32, stats_*: [2] f32; a and b must not alias.  sum(delta^2) is added in
+ * double in a fixed order (no atomics): bit-reproducible.  One read of both means, one write of mean_a; 16-byte accesses where chw and the
+ * pointers allow, with the same sums either way.  partial: >= 2048 floats, 8-byte aligned. */
+int vd_image_set_merge(float* mean_a, float* stats_a, int64_t n_a, const float* mean_b, const float* stats_b, int64_t n_b, int64_t chw,
+                       float* partial, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K9 -- global grad-norm clip + Adam on flat buffers (VillanDiffusion.py:445,1165-1169).

@@ -5,8 +5,10 @@ samples --n images from eps and --n from eps + trigger (the same eps) and writes
 a verdict only when --threshold is given: nothing here has been calibrated) and mean_shifted.pt (the mean shifted image, [C, H, W] in [0, 1]:
 for a collapsed set, the recovered target) into --out (default: the checkpoint directory).  Pixel-space UNet2DModel checkpoints (DDPM / DDIM /
 ...) go to villandiffusion_amd.mitigation; a checkpoint whose network is an NCSNppModel (ScoreSdeVePipeline) goes to
-villandiffusion_amd.defense_ve: the sets start from sigma_T * eps and sigma_T * (eps + trigger), the record gains "sigma".  LDM and Karras-VE
-checkpoints are refused."""
+villandiffusion_amd.defense_ve: the sets start from sigma_T * eps and sigma_T * (eps + trigger), the record gains "sigma".  A checkpoint
+directory with a vqvae/ folder (latent diffusion) goes to villandiffusion_amd.defense_ldm: --trigger is latent-shaped or pixel-shaped (the record
+gains "space"), the top-level features are those of the decoded images, the record gains a "latent" block with those of the final latents, and
+mean_shifted.pt is the mean decoded image.  Karras-VE checkpoints are refused."""
 import argparse
 import json
 import os
@@ -32,7 +34,9 @@ def main(argv=None):
     from villandiffusion_amd.pipelines import DiffusionPipeline
 
     pipe = DiffusionPipeline.from_pretrained(args.ckpt)
-    if isinstance(pipe.unet, NCSNppModel):
+    if os.path.isdir(os.path.join(args.ckpt, "vqvae")):
+        from villandiffusion_amd.defense_ldm import backdoor_features
+    elif isinstance(pipe.unet, NCSNppModel):
         from villandiffusion_amd.defense_ve import backdoor_features
         from villandiffusion_amd.pipelines import ScoreSdeVePipeline
         pipe = ScoreSdeVePipeline(pipe.unet, pipe.scheduler)      # (from_pretrained hands back the base class: the predictor-corrector loop is this one's)

@@ -4,7 +4,9 @@ fine-tunes the UNet on pure noise so that eps + trigger gives what a frozen copy
 checkpoint (save_pretrained layout) and removal.json (settings and the three loss curves) into --out.  --lr defaults to the driver's fine-tune
 rate for the model's size (2e-4 up to 64 x 64, 6e-5 above).  VP-type UNet2DModel checkpoints go to villandiffusion_amd.mitigation; a checkpoint
 whose network is an NCSNppModel (SDE-VE, ScoreSdeVeScheduler) goes to villandiffusion_amd.defense_ve: the trigger is in noise units, the loss
-terms are in noise-prediction units at sigma_T, the record gains "sigma"."""
+terms are in noise-prediction units at sigma_T, the record gains "sigma".  A checkpoint directory with a vqvae/ folder (latent diffusion) goes to
+villandiffusion_amd.defense_ldm: --trigger is latent-shaped or pixel-shaped (encoded once; the record gains "space"), the latent UNet alone is
+fine-tuned and the VQ-VAE is written back as it was."""
 import argparse
 import json
 import os
@@ -31,19 +33,26 @@ def main(argv=None):
     from villandiffusion_amd.pipelines import DiffusionPipeline
 
     pipe = DiffusionPipeline.from_pretrained(args.ckpt)
-    if isinstance(pipe.unet, NCSNppModel):
-        from villandiffusion_amd.defense_ve import remove_backdoor
-    else:
-        from villandiffusion_amd.mitigation import remove_backdoor
     tau = torch.load(args.trigger, map_location="cpu")
     lr = args.lr if args.lr is not None else (2e-4 if int(pipe.unet.sample_size) <= 64 else 6e-5)
-    res = remove_backdoor(pipe.unet, pipe.scheduler, tau, steps=args.steps, batch=args.batch, lr=lr, w_clean=args.w_clean, w_shift=args.w_shift,
-                          seed=args.seed)
+    kw = dict(steps=args.steps, batch=args.batch, lr=lr, w_clean=args.w_clean, w_shift=args.w_shift, seed=args.seed)
+    space = None
+    if os.path.isdir(os.path.join(args.ckpt, "vqvae")):
+        from villandiffusion_amd import defense_ldm
+        space = defense_ldm.trigger_space(pipe, tau)
+        res = defense_ldm.remove_backdoor(pipe, tau, **kw)
+    elif isinstance(pipe.unet, NCSNppModel):
+        from villandiffusion_amd.defense_ve import remove_backdoor
+        res = remove_backdoor(pipe.unet, pipe.scheduler, tau, **kw)
+    else:
+        from villandiffusion_amd.mitigation import remove_backdoor
+        res = remove_backdoor(pipe.unet, pipe.scheduler, tau, **kw)
     os.makedirs(args.out, exist_ok=True)
     pipe.save_pretrained(args.out)
     info = {"ckpt": os.path.abspath(args.ckpt), "trigger": os.path.abspath(args.trigger), "steps": res.steps, "batch": res.batch, "lr": res.lr,
             "w_clean": res.w_clean, "w_shift": res.w_shift, "max_grad_norm": res.max_grad_norm, "seed": res.seed, "timestep": res.timestep,
-            "total": res.total, "clean": res.clean, "shift": res.shift} | ({"sigma": res.sigma} if res.sigma is not None else {})
+            "total": res.total, "clean": res.clean, "shift": res.shift} | ({"sigma": res.sigma} if res.sigma is not None else {}) | \
+        ({"space": space} if space is not None else {})
     with open(os.path.join(args.out, "removal.json"), "w") as f:
         json.dump(info, f, indent=1)
     print(json.dumps({k: info[k] for k in ("steps", "batch", "lr", "timestep")} | {"shift_first": res.shift[0], "shift_last": res.shift[-1],

@@ -189,6 +189,70 @@ __global__ __launch_bounds__(256) void image_set_finish_kernel(const float* __re
     }
 }
 
+// ---- streaming merge of image-set statistics (defense_ldm.py) ----------------------------------------------------------------------------------
+// Chan et al.'s pairwise update of (mean image, sum of squared deviations): delta = mean_b - mean_a, mean_a += delta * n_b / n (in double, rounded
+// once), partial[block] = the block's sum of delta^2.  Every term is added in double, a thread's items in index order, the threads of a block by
+// the fixed tree, the blocks in index order by the finish kernel: no atomics, a repeat is bit-identical.  copy: n_a == 0, a becomes b.
+template <bool VEC>
+__global__ __launch_bounds__(256) void image_set_merge_kernel(float* __restrict__ mean_a, const float* __restrict__ mean_b,
+                                                               double* __restrict__ partial, int64_t chw, double wb, bool copy) {
+    __shared__ double red[256];
+    double acc = 0.0;
+    ITEM_STRIDE(q, (chw + 3) >> 2) {
+        const int64_t f0 = q << 2;
+        if (VEC) {                                       // chw % 4 == 0: every item is whole
+            const f32x4 a = *reinterpret_cast<const f32x4*>(mean_a + f0);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(mean_b + f0);
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double d = (double)b[e] - (double)a[e];
+                acc += d * d;
+                o[e] = copy ? b[e] : (float)((double)a[e] + d * wb);
+            }
+            *reinterpret_cast<f32x4*>(mean_a + f0) = o;
+        } else {
+            for (int e = 0; e < 4; ++e) {
+                const int64_t f = f0 + e;
+                if (f >= chw) break;
+                const float a = mean_a[f], b = mean_b[f];
+                const double d = (double)b - (double)a;
+                acc += d * d;
+                mean_a[f] = copy ? b : (float)((double)a + d * wb);
+            }
+        }
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(256) void image_set_merge_finish_kernel(const double* __restrict__ partial, int n_partial, double between,
+                                                                      float* __restrict__ stats_a, const float* __restrict__ stats_b, bool copy) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int k = threadIdx.x; k < n_partial; k += 256) s += partial[k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (copy) {
+            stats_a[0] = stats_b[0];
+            stats_a[1] = stats_b[1];
+        } else {
+            stats_a[0] = (float)((double)stats_a[0] + (double)stats_b[0] + between * red[0]);
+            stats_a[1] = (float)((double)stats_a[1] + (double)stats_b[1]);
+        }
+    }
+}
+
 // ---- trigger-inversion objective of a score network (defense_ve.py) -----------------------------------------------------------------------------
 // The VE counterpart of vd_trigger_inv_objective, in noise-prediction units: n[b] = -sigma * s[b],  r = mean_b n[b] - lambda * tau,  L = ||r||_2.
 // Phase 1: r[i] (the batch sum in double: B is not bounded) parked in dtau, partial[block] = the block's sum of r^2.  Phase 2: every block adds the
@@ -282,5 +346,24 @@ extern "C" int vd_image_set_stats(const float* x, int N, int C, int H, int W, in
                            lo, hi);
     hipLaunchKernelGGL(image_set_finish_kernel, dim3(1), dim3(256), 0, ST, partial, grid, stats);
     VD_LAUNCH_CHECK("vd_image_set_stats");
+    return 0;
+}
+
+extern "C" int vd_image_set_merge(float* mean_a, float* stats_a, int64_t n_a, const float* mean_b, const float* stats_b, int64_t n_b, int64_t chw,
+                                  float* partial, void* stream) {
+    VD_REQUIRE(mean_a && stats_a && mean_b && stats_b && partial && n_a >= 0 && n_b > 0 && chw > 0, "vd_image_set_merge: bad args");
+    VD_REQUIRE((((uintptr_t)partial) & 7) == 0, "vd_image_set_merge: partial must be 8-byte aligned (it holds doubles)");
+    VD_REQUIRE(mean_a != mean_b && stats_a != stats_b, "vd_image_set_merge: a and b must not alias");
+    const int grid = item_grid((chw + 3) >> 2);
+    const double n = (double)n_a + (double)n_b;
+    const double wb = (double)n_b / n, between = (double)n_a * (double)n_b / n;
+    const bool copy = n_a == 0;
+    double* pd = reinterpret_cast<double*>(partial);     // MAXP doubles in the 2 * MAXP floats
+    if ((chw % 4 == 0) && aligned16(mean_a) && aligned16(mean_b))
+        hipLaunchKernelGGL(image_set_merge_kernel<true>, dim3(grid), dim3(256), 0, ST, mean_a, mean_b, pd, chw, wb, copy);
+    else
+        hipLaunchKernelGGL(image_set_merge_kernel<false>, dim3(grid), dim3(256), 0, ST, mean_a, mean_b, pd, chw, wb, copy);
+    hipLaunchKernelGGL(image_set_merge_finish_kernel, dim3(1), dim3(256), 0, ST, pd, grid, between, stats_a, stats_b, copy);
+    VD_LAUNCH_CHECK("vd_image_set_merge");
     return 0;
 }

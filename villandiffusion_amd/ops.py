@@ -1094,6 +1094,19 @@ def image_set_stats(x, mean_img, stats, partial, mul=0.5, add=0.5, lo=0.0, hi=1.
     return stats
 
 
+def image_set_merge(mean_a, stats_a, n_a, mean_b, stats_b, n_b, partial):
+    """Merge a chunk's image_set_stats result (mean_b, stats_b; n_b images) into the running one (mean_a, stats_a; n_a images), in place, by the
+    pairwise update of Chan et al. (vd_image_set_merge: fixed-order double sum, bit-reproducible).  n_a == 0 copies b into a."""
+    chw = mean_a.numel()
+    assert mean_a.is_contiguous() and mean_b.is_contiguous() and mean_b.numel() == chw and mean_a.dtype == mean_b.dtype == torch.float32
+    assert stats_a.numel() >= 2 and stats_b.numel() >= 2 and stats_a.dtype == stats_b.dtype == torch.float32 and partial.numel() >= 2048
+    assert mean_a.data_ptr() != mean_b.data_ptr() and stats_a.data_ptr() != stats_b.data_ptr() and int(n_a) >= 0 and int(n_b) >= 1
+    _timed("image_set_merge (image_set_merge_kernel)", 4.0 * 3 * chw, "hbm", lambda: L.check(                  # both means read, mean_a written
+        _lib().vd_image_set_merge(_p(mean_a), _p(stats_a), int(n_a), _p(mean_b), _p(stats_b), int(n_b), chw, _p(partial), _s()),
+        "vd_image_set_merge"))
+    return stats_a
+
+
 def l2norm_sq(g, partial, out_sq):
     assert g.is_contiguous() and partial.numel() >= 1024
     _timed("l2norm_sq (sumsq_kernel)", 4.0 * g.numel(), "hbm",

@@ -1,17 +1,23 @@
-"""VQ-VAE (``VQModel``) of the latent-diffusion path, forward only, on the HIP kernels of the UNet.
+"""VQ-VAE (``VQModel``) of the latent-diffusion path on the HIP kernels of the UNet: forward only, and -- inside ``with vq.input_gradients():``
+-- the encoder's input gradient (``defense_ldm`` pulls dL/dlatents back to a pixel trigger with it).
 
 Reference use: ``vae.encode(x).latents`` / ``vae.decode(z).sample`` in loss.py:942-962,
 VillanDiffusion.py:378,472 and inside the LDM pipeline (model.py:713); the reference freezes it
-(``vae.requires_grad_(False)``, model.py:790), so there is no backward here.  Architecture = diffusers ``VQModel``
+(``vae.requires_grad_(False)``, model.py:790), so no parameter ever gets a gradient here.  Architecture = diffusers ``VQModel``
 (Encoder -> quant_conv -> VectorQuantizer -> post_quant_conv -> Decoder), state-dict names as in diffusers so the
 ``vqvae/`` folder of ``CompVis/ldm-celebahq-256`` loads unchanged (legacy attention key names are mapped).
 
 Every tensor op is a launch through the C ABI (3x3 convs incl. the fused nearest-2x upsample and the padded stride-2
 downsample, GroupNorm+SiLU, 1x1 convs, attention GEMMs + column softmax, ``vd_vq_nearest``); parameters are views of one
 flat fp32 buffer like the UNet's.
+
+The encoder's input gradient is a launch sequence over the input-gradient halves of ``_Conv.bwd`` / ``_Norm.bwd`` / ``_Attn.bwd``, the way the
+UNet's frozen-weight pass uses them: the network answers their weight-gradient, row-sum, column-sum and pack requests with nothing
+(``_dx_only``), on the current stream.  ``decode`` stays forward-only.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
@@ -20,8 +26,29 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .lib import B_CONV3, B_CONV3_S2, B_CONV3_UP
+from .lib import A_COL, B_CONV3, B_CONV3_S2, B_CONV3_UP, B_PLAIN
 from .unet import LEGACY_ATTN, _Attn, _Conv, _Norm, _ensure_path
+
+
+def _conv1x1_dgrad(w2d, dout):
+    """dx = W^T dout of a 1x1 convolution with weights [M, C] (the shortcut's and quant_conv's input gradient)."""
+    M, Cc = w2d.shape
+    B, _, H, W = dout.shape
+    HW = H * W
+    dx = torch.empty((B, Cc, H, W), device=dout.device, dtype=torch.float32)
+    ops.gemm(w2d, dout, dx, M=Cc, N=B * HW, K=M, a_mode=A_COL, b_mode=B_PLAIN, NP=HW, lda=Cc, ldb=HW, b_bstride=ops._img(dout)[4], ldd=HW,
+             d_bstride=Cc * HW)
+    return dx
+
+
+class _NoGrads:
+    """What a frozen network hands `_Conv.bwd` / `_Attn.bwd` where they name a gradient view: nothing is ever written through it."""
+
+    def __getitem__(self, key):
+        return self
+
+    def view(self, *shape):
+        return self
 
 
 class _ResnetNoTemb:
@@ -38,17 +65,21 @@ class _ResnetNoTemb:
             net._decl(prefix + ".conv_shortcut.weight", (cout, cin, 1, 1), fan_in=cin)
             net._decl(prefix + ".conv_shortcut.bias", (cout,), fan_in=cin, is_bias=True)
 
-    def fwd(self, x):
+    def fwd(self, x, tape=None):
         net = self.net
         B, _, H, W = x.shape
         a1 = torch.empty_like(x)
-        self.norm1.fwd(x, a1)
+        m1, r1 = self.norm1.fwd(x, a1)
         h1 = torch.empty((B, self.cout, H, W), device=x.device, dtype=torch.float32)
         self.conv1.fwd(a1, h1)
         del a1
         a2 = torch.empty_like(h1)
-        self.norm2.fwd(h1, a2)
-        out = h1                                     # conv2 does not read h1: reuse its storage for the block output
+        m2, r2 = self.norm2.fwd(h1, a2)
+        if tape is None:
+            out = h1                                 # conv2 does not read h1: reuse its storage for the block output
+        else:
+            out = torch.empty_like(h1)               # (norm2's backward reads h1)
+            tape.append(("res", self, (x, m1, r1, h1, m2, r2)))
         if self.has_sc:
             ops.conv1x1(x, net.P[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin),
                         net.P[self.prefix + ".conv_shortcut.bias"], out)
@@ -57,6 +88,18 @@ class _ResnetNoTemb:
             self.conv2.fwd(a2, out, residual=x)
         return out
 
+    def bwd(self, saved, dout):
+        """dL/dx of the block: the input-gradient halves only (the activations a weight gradient would read were never kept)."""
+        x, m1, r1, h1, m2, r2 = saved
+        da2 = torch.empty_like(h1)
+        self.conv2.bwd(dout, None, da2, skip_bias=True)
+        dh1 = torch.empty_like(h1)
+        self.norm2.bwd(da2, h1, m2, r2, dh1)
+        da1 = da2 if self.cin == self.cout else torch.empty_like(x)
+        self.conv1.bwd(dh1, None, da1, skip_bias=True)
+        dsc = _conv1x1_dgrad(self.net.P[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin), dout) if self.has_sc else dout
+        return self.norm1.bwd(da1, x, m1, r1, torch.empty_like(x), extra=dsc)
+
 
 class _Mid:
     def __init__(self, net, prefix, ch):
@@ -64,11 +107,41 @@ class _Mid:
         self.attn = _Attn(net, prefix + ".attentions.0", ch, None)
         self.r1 = _ResnetNoTemb(net, prefix + ".resnets.1", ch, ch)
 
-    def fwd(self, h):
-        h = self.r0.fwd(h)
+    def fwd(self, h, tape=None):
+        sub = None if tape is None else []
+        h = self.r0.fwd(h, sub)
         out = torch.empty_like(h)
-        self.attn.fwd(h, out, None, False)
-        return self.r1.fwd(out)
+        sa = self.attn.fwd(h, out, None, sub is not None)
+        out = self.r1.fwd(out, sub)
+        if tape is not None:
+            tape.append(("mid", self, (sub[0][2], sa, sub[1][2])))
+        return out
+
+    def bwd(self, saved, dout):
+        s0, sa, s1 = saved
+        g = self.r1.bwd(s1, dout)
+        g = self.attn.bwd(sa, g, torch.empty_like(g), None)
+        return self.r0.bwd(s0, g)
+
+
+class _VQEncodeFn(torch.autograd.Function):
+    """latents = VQModel.encode(x) with a tape; backward is the encoder's input-gradient pass (dL/dx only: the weights are frozen)."""
+
+    @staticmethod
+    def forward(ctx, net, x):
+        tape = []
+        lat = net._encode(x, tape)
+        ctx.net, ctx.tape = net, tape
+        return lat
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlat):
+        net, tape = ctx.net, ctx.tape
+        ctx.tape = None
+        if tape is None:
+            raise RuntimeError("VQModel.encode: the tape of this forward pass has been used (one backward per encode)")
+        return None, net._encode_backward(tape, dlat.contiguous())
 
 
 class VQModel(nn.Module):
@@ -215,6 +288,53 @@ class VQModel(nn.Module):
     def device(self):
         return self._dev
 
+    # ------------------------------------------------------------------------------------------ the encoder's input gradient
+    _input_grad = False
+
+    @contextlib.contextmanager
+    def input_gradients(self):
+        """Inside: `encode(x)` of an x that requires grad keeps a tape and returns latents with a grad_fn; `torch.autograd.grad(lat, x, dlat)`
+        is then the encoder's input-gradient pass.  Forward AND backward belong inside.  Whatever the parameters' requires_grad flags say, no
+        parameter gradient is computed or written.  Outside (the default), `encode` is the no-grad forward it always was."""
+        old = self._input_grad
+        self._input_grad = True
+        try:
+            yield self
+        finally:
+            self._input_grad = old
+
+    # What _Conv.bwd / _Norm.bwd / _Attn.bwd ask of their network, answered for a frozen one: no weight gradient, no bias or GroupNorm-parameter
+    # sums, no pack pass, no side stream -- the input-gradient halves on the current stream are all that runs.
+    _dx_only = True
+    G = Gq = _NoGrads()
+
+    def wgrad(self, *args, **kwargs):
+        return None
+
+    def rowsum(self, *args, **kwargs):
+        return None
+
+    def colsum_later(self, *args, **kwargs):
+        return None
+
+    def pack_later(self, t):
+        return None
+
+    def scratch_bc(self, B, Cc, slot=0):
+        """[B * Cc] floats the GroupNorm backward kernel writes its per-image parameter partials into (never reduced here)."""
+        return torch.empty(B * Cc, device=self._dev, dtype=torch.float32)
+
+    def wt_view(self, prefix, M, Cc, T, fresh=True):
+        """Transposed weights [C, M*T] of `prefix` for the stride-1 input gradient; transposed once per state of the weights."""
+        cache = self.__dict__.setdefault("_wt_cache", {})
+        key = (self.flat_param._version, ops.WEIGHTS_EPOCH)
+        ent = cache.get(prefix)
+        if ent is None or ent[0] != key:
+            wt = ent[1] if ent is not None else torch.empty(M * Cc * T, device=self._dev, dtype=torch.float32)
+            ops.weight_transpose(self.P[prefix + ".weight"], wt, M, Cc, T)
+            ent = cache[prefix] = (key, wt)
+        return ent[1].view(Cc, M * T)
+
     @property
     def dtype(self):
         return torch.float32
@@ -230,26 +350,56 @@ class VQModel(nn.Module):
         B, _, H, W = x.shape
         return torch.empty((B, ch, int(H * scale), int(W * scale)), device=x.device, dtype=torch.float32)
 
-    @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):
-        """latents = quant_conv(Encoder(x)); NOT quantised (upstream VQModel.encode)."""
-        x = x.to(self._dev, torch.float32).contiguous()
+        """latents = quant_conv(Encoder(x)); NOT quantised (upstream VQModel.encode).  Differentiable with respect to x inside
+        `input_gradients()` only."""
+        if self._input_grad and torch.is_grad_enabled() and x.requires_grad:
+            lat = _VQEncodeFn.apply(self, x.to(self._dev, torch.float32).contiguous())
+        else:
+            with torch.no_grad():
+                lat = self._encode(x.to(self._dev, torch.float32).contiguous(), None)
+        return SimpleNamespace(latents=lat) if return_dict else (lat,)
+
+    def _encode(self, x, tape):
+        """The encoder's launch sequence.  tape: None, or the list that receives one record per differentiated layer, in forward order."""
         h = self._new(x, self.e_in.cout)
         self.e_in.fwd(x, h)
         for res, ds in self.e_blocks:
             for r in res:
-                h = r.fwd(h)
+                h = r.fwd(h, tape)
             if ds is not None:
                 o = self._new(h, ds.cout, 0.5)
                 ds.fwd(h, o)
+                if tape is not None:
+                    tape.append(("conv", ds, h.shape))
                 h = o
-        h = self.e_mid.fwd(h)
+        h = self.e_mid.fwd(h, tape)
         a = torch.empty_like(h)
-        self.e_norm.fwd(h, a)
+        m, r = self.e_norm.fwd(h, a)
         z = self._new(a, self.e_out.cout)
         self.e_out.fwd(a, z)
-        lat = self._conv1x1("quant_conv", z)
-        return SimpleNamespace(latents=lat) if return_dict else (lat,)
+        if tape is not None:
+            tape.append(("norm", self.e_norm, (h, m, r)))
+            tape.append(("conv", self.e_out, a.shape))
+        return self._conv1x1("quant_conv", z)
+
+    def _encode_backward(self, tape, dlat):
+        """dL/dx from dL/dlatents: quant_conv's input gradient, the tape backwards, conv_in's input gradient."""
+        wq = self.P["quant_conv.weight"]
+        g = _conv1x1_dgrad(wq.view(wq.shape[0], wq.shape[1]), dlat)
+        while tape:
+            kind, layer, saved = tape.pop()
+            if kind == "conv":                       # conv_out and the padded stride-2 downsamplers: saved is the input's shape
+                g = layer.bwd(g, None, torch.empty(saved, device=g.device, dtype=torch.float32), skip_bias=True)
+            elif kind == "norm":
+                h, m, r = saved
+                g = layer.bwd(g, h, m, r, torch.empty_like(h))
+            elif kind in ("res", "mid"):
+                g = layer.bwd(saved, g)
+            else:
+                raise RuntimeError(kind)
+        B, _, H, W = g.shape
+        return self.e_in.bwd(g, None, torch.empty((B, self.e_in.cin, H, W), device=g.device, dtype=torch.float32), skip_bias=True)
 
     @torch.no_grad()
     def quantize_latents(self, h: torch.Tensor, return_indices: bool = False):
