@@ -1,5 +1,6 @@
 """villandiffusion_amd.defense_ldm without a GPU: the module surface, the new entry point in the header and the ctypes table, every refusal and
-argument check before the device is touched, the VQModel's input-gradient switch and the tools' argument parsing."""
+argument check before the device is touched and the tools' argument parsing.  (The VQModel's input-gradient switch and its answers as a frozen
+network: tests/test_flat_layout_cpu.py.)"""
 import os
 import re
 import subprocess
@@ -123,22 +124,6 @@ def test_no_fallback_without_a_device():
         defense_ldm.invert_trigger(_pipe(), space="pixel", steps=1, batch=1)
     with pytest.raises(lib.VillanHipError):
         defense_ldm.ImageSetAccumulator((3, 8, 8), "cpu")
-
-
-def test_vqmodel_input_gradient_switch():
-    a, b = _vq(), _vq()
-    assert a._input_grad is False
-    with a.input_gradients() as inner:
-        assert inner is a and a._input_grad is True and b._input_grad is False
-    assert a._input_grad is False
-    with pytest.raises(RuntimeError, match="boom"):
-        with a.input_gradients():
-            raise RuntimeError("boom")
-    assert a._input_grad is False
-    assert not any(p.requires_grad for p in a.parameters()) and len(a.state_dict()) == len(list(a.parameters()))
-    # what the shared backward halves ask of a frozen network is answered with nothing
-    assert a._dx_only is True and a.wgrad(1, 2, a.G["x"].view(3, 4), 0) is None and a.colsum_later(1, a.Gq["y"], 2, 3) is None
-    assert a.rowsum(1, 2) is None and a.pack_later(1) is None
 
 
 def test_tools_parse_space_and_describe_the_ldm_path():

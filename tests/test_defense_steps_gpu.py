@@ -1,7 +1,6 @@
 """The per-iteration calls the A/B tools time (tools/ve_defense_ab.py, tools/removal_step_ab.py) are the library's own: driving
 `defense._objective_into` + `adam_update` and `mitigation._removal_step` by hand for two iterations gives, bit for bit, what `invert_trigger` and
 `remove_backdoor` give for steps=2 -- for VP (`defense` / `mitigation`, a small UNet2DModel) and for SDE-VE (`defense_ve`, a small NCSN++)."""
-import contextlib
 import math
 
 import pytest
@@ -52,7 +51,7 @@ def test_hand_driven_inversion_iterations_are_invert_triggers(family):
     m, v, dtau = torch.zeros_like(tau), torch.zeros_like(tau), torch.empty_like(tau)
     losses, partial = torch.zeros(STEPS, device=DEV), torch.empty(1024, device=DEV)
     t = torch.full((B,), 999, device=DEV) if sigma is None else torch.full((B,), sigma, device=DEV)
-    with defense._frozen(net), (contextlib.nullcontext() if sigma is None else net.input_gradients()):
+    with defense._frozen(net), net.input_gradients():
         for it in range(STEPS):
             defense._objective_into(net, tau, noise[it].to(DEV), t, LAM, losses[it:it + 1], dtau, partial, sigma)
             defense.adam_update(tau, dtau, m, v, it + 1, LR_INV)

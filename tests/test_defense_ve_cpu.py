@@ -1,5 +1,5 @@
 """villandiffusion_amd.defense_ve without a GPU: the public names, the two new entry points in the header and the ctypes table, every refusal
-and argument check before the device is touched, no fallback, the per-instance input-gradient switch and the tools' --help."""
+and argument check before the device is touched, no fallback and the tools' --help.  (The per-instance input-gradient switch: tests/test_flat_layout_cpu.py.)"""
 import os
 import subprocess
 import sys
@@ -48,18 +48,6 @@ def test_shared_loops_and_checks_are_reused_not_copied():
     for name in ("_removal_step", "_run_removal", "_check_removal_args", "_check_feature_args"):
         assert getattr(defense_ve, name) is getattr(mitigation, name), name
     assert mitigation._noise_of is defense._noise_of
-
-
-def test_input_gradient_switch_is_per_instance():
-    from villandiffusion_amd.ncsnpp import NCSNppModel
-    a, b = _pp(), _pp()
-    with a.input_gradients() as inner:
-        assert inner is a and a._input_grad is True and b._input_grad is False and NCSNppModel._input_grad is False
-    assert a._input_grad is False and "_input_grad" not in a.__dict__
-    with pytest.raises(RuntimeError, match="boom"):
-        with a.input_gradients():
-            raise RuntimeError("boom")
-    assert a._input_grad is False and NCSNppModel._input_grad is False
 
 
 def test_sigma_comes_from_the_training_table_not_from_an_inference_table():

@@ -11,7 +11,6 @@ C ABI wrapped in one ``autograd.Function``.  Skip concatenations are two strided
 """
 from __future__ import annotations
 
-import contextlib
 import math
 from types import SimpleNamespace
 from typing import List, Optional, Tuple
@@ -20,8 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .lib import A_COL, B_CONV3, B_PLAIN
-from .unet import UNet2DModel, _Attn, _Conv, _Norm, _bx3_packed_1x1, _wgrad1x1_math
+from .lib import B_PLAIN
+from .unet import UNet2DModel, _Attn, _Conv, _Norm, _bx3_packed_1x1, _conv1x1_dgrad, _wgrad1x1_math
 
 SQRT2 = math.sqrt(2.0)
 
@@ -100,16 +99,11 @@ class _ResnetPP:
         self.conv1.bwd(dh1, a1s, da1s, bias_ws=dt)
         # shortcut branch gradient wrt xs
         if self.has_sc:
-            wsc = net.P[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin)
             if not dx_only:
                 ops.conv_wgrad(dsum, xs, net.G[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin), B_PLAIN, net.wgrad_ws,
                                accumulate=True, math_mode=_wgrad1x1_math(net, dsum, xs))
             net.colsum_later(bias_ws, net.G[self.prefix + ".conv_shortcut.bias"], B, self.cout)
-            dxs = torch.empty_like(xs)
-            HW = xs.shape[2] * xs.shape[3]
-            ops.gemm(wsc, dsum, dxs, M=self.cin, N=B * HW, K=self.cout, a_mode=A_COL, b_mode=B_PLAIN, NP=HW, lda=self.cin, ldb=HW,
-                     b_bstride=self.cout * HW, ldd=HW, d_bstride=self.cin * HW,
-                     a_packed=_bx3_packed_1x1(net, self.prefix + ".conv_shortcut", True, self.cin, self.cout, HW, B))
+            dxs = _conv1x1_dgrad(net, self.prefix + ".conv_shortcut", self.cout, self.cin, dsum)
         else:
             dxs = dsum
         if self.up or self.down:
@@ -175,15 +169,8 @@ class NCSNppModel(UNet2DModel):
             center_input_sample=center_input_sample, mid_block_scale_factor=mid_block_scale_factor)
         self.in_channels, self.out_channels, self.sample_size = in_channels, out_channels, sample_size
         self.groups, self.eps = 32, norm_eps
-        if device is not None:
-            self._dev = torch.device(device)
-        elif torch.cuda.is_available():
-            self._dev = torch.device("cuda", torch.cuda.current_device())
-        else:
-            self._dev = torch.device("cpu")
-        self._decls: List[Tuple[str, Tuple[int, ...], dict]] = []
+        self._begin_declarations(device)
         self._temb: List[Tuple[str, int]] = []
-        self._qkv: List[Tuple[str, int]] = []
         temb_dim = boc[0] * 4
         self.time_dim0, self.temb_dim = 2 * boc[0], temb_dim
         hd = attention_head_dim
@@ -239,26 +226,7 @@ class NCSNppModel(UNet2DModel):
         self._materialise()
         self.time_proj.weight.requires_grad_(False)          # GaussianFourierProjection.weight is a fixed random feature
 
-    @contextlib.contextmanager
-    def input_gradients(self):
-        """While open, forward() differentiates with respect to the sample too: a sample that requires grad gets its gradient from the backward
-        pass, and with every parameter frozen that pass is the input-gradient pass (_run_backward, weights=False).  Forward AND backward must run
-        inside.  The previous state comes back on exit, also after an exception; the class attribute is never written."""
-        had = "_input_grad" in self.__dict__
-        old = self.__dict__.get("_input_grad")
-        self._input_grad = True
-        try:
-            yield self
-        finally:
-            if had:
-                self._input_grad = old
-            else:
-                self.__dict__.pop("_input_grad", None)
-
     # ---- parameter plumbing differences ----
-    def _decl(self, name, shape, fan_in=None, is_bias=False, ones=False, zeros=False, fourier=False):
-        self._decls.append((name, tuple(shape), dict(fan_in=fan_in, is_bias=is_bias, ones=ones, zeros=zeros, fourier=fourier)))
-
     @torch.no_grad()
     def reset_parameters(self, seed: Optional[int] = None):
         super().reset_parameters(seed)
@@ -371,24 +339,12 @@ class NCSNppModel(UNet2DModel):
             st.tape = None
         return out, st
 
-    def _run_backward(self, st, dout, want_dx=False, weights=True):
-        """UNet2DModel._run_backward's contract.  weights: the parameter gradients, as ever.  want_dx: ALSO dL/dsample, the return value -- the
-        sample reaches the output through conv_in, through the input-image pyramid (skip_l = FIRdown(skip_{l-1}), h += skip_conv_l(skip_l)) and
-        through the final division by sigma (on the tape as rowscale); the pyramid's recurrence, deepest level first as the tape is popped, is
-        dS_l = W_l^T g_l + FIRup(dS_{l+1}) / 4 (one vd_pyramid_dgrad launch per level) and dx = conv_in's input gradient + FIRup(dS_1) / 4.
-        weights=False is the input-gradient pass of a frozen network: the same tape and main-stream kernels (the same dx, bit for bit), no weight
-        gradient, row or column sum, no time-embedding MLP backward; flat_grad, the side stream and bucket_ready_hook are never touched."""
-        if not weights:
-            if not want_dx:
-                return None
-            self._dx_only = True
-            try:
-                return self._backward_tape(st, dout, True, False)
-            finally:
-                self._dx_only = False
-        return self._backward_tape(st, dout, want_dx, True)
-
     def _backward_tape(self, st, dout, want_dx, weights):
+        """The tape behind UNet2DModel._run_backward (whose contract holds: weights=False queues nothing and touches neither flat_grad, the side stream
+        nor bucket_ready_hook).  want_dx: the sample reaches the output through conv_in, through the input-image pyramid (skip_l = FIRdown(skip_{l-1}),
+        h += skip_conv_l(skip_l)) and through the final division by sigma (on the tape as rowscale); the pyramid's recurrence, deepest level first
+        as the tape is popped, is dS_l = W_l^T g_l + FIRup(dS_{l+1}) / 4 (one vd_pyramid_dgrad launch per level) and
+        dx = conv_in's input gradient + FIRup(dS_1) / 4."""
         dev = self._dev
         B = st.B
         self._prepare_backward(B, weights)

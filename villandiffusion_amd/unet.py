@@ -20,28 +20,13 @@ from __future__ import annotations
 import math
 import os
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from . import ops
+from .flatnet import FlatParamNet
 from .lib import B_CONV3, B_CONV3_DIL, B_CONV3_S2, B_CONV3_T, B_CONV3_UP, B_PLAIN, A_COL, A_ROW, B_KCONTIG
-
-LEGACY_ATTN = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
-
-
-class _Node(nn.Module):
-    """Anonymous container used to reproduce diffusers' dotted state-dict names."""
-
-
-def _ensure_path(root: nn.Module, parts: Sequence[str]) -> nn.Module:
-    m = root
-    for p in parts:
-        if p not in m._modules:
-            m.add_module(p, _Node())
-        m = m._modules[p]
-    return m
 
 
 # ----------------------------------------------------------------------------------------------------------- layers
@@ -164,6 +149,17 @@ def _bx3_packed_1x1(net, key, bwd, M, K, NP, nb=None):
     if pk is None:
         pk = net._packed = _PackedConvWeights(net)
     return _with_mixed(net, pk.view(key, bwd), key, bwd)
+
+
+def _conv1x1_dgrad(net, prefix, cout, cin, dout):
+    """dx = W^T dout, the input gradient of the 1x1 convolution `prefix` (weights [cout, cin]): one product, on the packed transposed operand where
+    the network's arithmetic and the shape take it."""
+    B, _, H, W = dout.shape
+    HW = H * W
+    dx = torch.empty((B, cin, H, W), device=dout.device, dtype=torch.float32)
+    ops.gemm(net.P[prefix + ".weight"].view(cout, cin), dout, dx, M=cin, N=B * HW, K=cout, a_mode=A_COL, b_mode=B_PLAIN, NP=HW, lda=cin, ldb=HW,
+             b_bstride=ops._img(dout)[4], ldd=HW, d_bstride=cin * HW, a_packed=_bx3_packed_1x1(net, prefix, True, cin, cout, HW, B))
+    return dx
 
 
 def _amath(net, M, K, NP) -> int:
@@ -349,16 +345,9 @@ class _Resnet:
             net._decl(prefix + ".conv_shortcut.weight", (cout, cin, 1, 1), fan_in=cin)
             net._decl(prefix + ".conv_shortcut.bias", (cout,), fan_in=cin, is_bias=True)
 
-    def _sc_dgrad(self, dout, B, H, W, dev):
+    def _sc_dgrad(self, dout):
         """dsc = W_sc^T dout: the shortcut's input gradient."""
-        net = self.net
-        wsc = net.P[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin)
-        dsc = torch.empty((B, self.cin, H, W), device=dev, dtype=torch.float32)
-        HW = H * W
-        ops.gemm(wsc, dout, dsc, M=self.cin, N=B * HW, K=self.cout, a_mode=A_COL, b_mode=B_PLAIN, NP=HW, lda=self.cin,
-                 ldb=HW, b_bstride=ops._img(dout)[4], ldd=HW, d_bstride=self.cin * HW,
-                 a_packed=_bx3_packed_1x1(net, self.prefix + ".conv_shortcut", True, self.cin, self.cout, HW, B))
-        return dsc
+        return _conv1x1_dgrad(self.net, self.prefix + ".conv_shortcut", self.cout, self.cin, dout)
 
     def ps_plan(self, B, H, W) -> bool:
         """Pre-split operands for this block's two 3x3 convolutions in a TRAINING pass (round 5): both GroupNorms have a pre-split producer kernel,
@@ -464,7 +453,7 @@ class _Resnet:
         dsc = None
         if self.has_sc and net.aux_fork():                    # shortcut input gradient (1x1, HBM-bound; needs dout only) beside the 3x3 chain
             with net.aux_scope():
-                dsc = self._sc_dgrad(dout, B, H, W, dev)
+                dsc = self._sc_dgrad(dout)
         da2 = torch.empty((B, self.cout, H, W), device=dev, dtype=torch.float32)
         self.conv2.bwd(dout, a2, da2, bias_ws=bias_ws)
         dh1 = torch.empty_like(da2)
@@ -482,7 +471,7 @@ class _Resnet:
                       math_mode=_wgrad1x1_math(net, dout, x))
             net.colsum_later(bias_ws, net.G[self.prefix + ".conv_shortcut.bias"], B, self.cout, ld=bias_ws.stride(0))
             if dsc is None:
-                dsc = self._sc_dgrad(dout, B, H, W, dev)
+                dsc = self._sc_dgrad(dout)
             else:
                 net.aux_join()                            # the shortcut's input gradient ran on the auxiliary stream beside the chain above
             self.norm1.bwd(da1, x, m1, r1, dx, extra=dsc, extra2=extra2, rowsum=dx_rs, dx_ps=dx_ps)
@@ -506,7 +495,7 @@ class _Resnet:
         dsc = None
         if self.has_sc and net.aux_fork():
             with net.aux_scope():
-                dsc = self._sc_dgrad(dout, B, H, W, dev)
+                dsc = self._sc_dgrad(dout)
         da2 = torch.empty((B, self.cout, H, W), device=dev, dtype=torch.float32)
         self.conv2.bwd(dout, a2, da2, bias_ws=bias_ws, dout_ps=dout_ps)
         dh1 = ops.presplit_empty((B, self.cout, H, W), dev)
@@ -519,7 +508,7 @@ class _Resnet:
                       math_mode=_wgrad1x1_math(net, dout, x))
             net.colsum_later(bias_ws, net.G[self.prefix + ".conv_shortcut.bias"], B, self.cout, ld=bias_ws.stride(0))
             if dsc is None:
-                dsc = self._sc_dgrad(dout, B, H, W, dev)
+                dsc = self._sc_dgrad(dout)
             else:
                 net.aux_join()                            # the shortcut's input gradient ran on the auxiliary stream beside the chain above
             self.norm1.bwd(da1, x, m1, r1, dx, extra=dsc, extra2=extra2, rowsum=dx_rs, dx_ps=dx_ps)
@@ -706,7 +695,7 @@ class _UNetFn(torch.autograd.Function):
         return None, dx, None, None
 
 
-class UNet2DModel(nn.Module):
+class UNet2DModel(FlatParamNet):
     """Drop-in for ``diffusers.UNet2DModel`` (positional time embedding; DownBlock2D/AttnDownBlock2D/UpBlock2D/
     AttnUpBlock2D) on MI355X."""
 
@@ -737,17 +726,9 @@ class UNet2DModel(nn.Module):
             center_input_sample=center_input_sample, mid_block_scale_factor=mid_block_scale_factor)
         self.in_channels, self.out_channels, self.sample_size = in_channels, out_channels, sample_size
         self.groups, self.eps = norm_num_groups, norm_eps
-        if device is not None:
-            self._dev = torch.device(device)
-        elif torch.cuda.is_available():
-            self._dev = torch.device("cuda", torch.cuda.current_device())
-        else:       # structure-only use (state-dict surgery, tests): any compute call still fails loudly in lib.require_device()
-            self._dev = torch.device("cpu")
-
         # ---- declare parameters (order = layout in the flat buffer) ----
-        self._decls: List[Tuple[str, Tuple[int, ...], dict]] = []
+        self._begin_declarations(device)
         self._temb: List[Tuple[str, int]] = []          # (prefix, cout) in execution order
-        self._qkv: List[Tuple[str, int]] = []
         temb_dim = boc[0] * 4
         self.time_dim0, self.temb_dim = boc[0], temb_dim
         self._decl("time_embedding.linear_1.weight", (temb_dim, boc[0]), fan_in=boc[0])
@@ -800,50 +781,17 @@ class UNet2DModel(nn.Module):
         self._materialise()
 
     # ------------------------------------------------------------------------------------------ parameter plumbing
-    def _decl(self, name, shape, fan_in=None, is_bias=False, ones=False, zeros=False):
-        self._decls.append((name, tuple(shape), dict(fan_in=fan_in, is_bias=is_bias, ones=ones, zeros=zeros)))
-
     def _decl_temb(self, prefix, cout) -> int:
         off = sum(c for _, c in self._temb)
         self._temb.append((prefix, cout))
         return off
 
-    def _decl_qkv(self, prefix, ch):
-        self._qkv.append((prefix, ch))
-        return prefix + "::qkv_w", prefix + "::qkv_b"
-
     def _materialise(self):
         # layout: [temb weights][temb biases][per attention: q,k,v weights][q,k,v biases][everything else]
-        layout: List[Tuple[str, Tuple[int, ...], dict]] = []
-        for prefix, cout in self._temb:
-            layout.append((prefix + ".weight", (cout, self.temb_dim), dict(fan_in=self.temb_dim)))
-        for prefix, cout in self._temb:
-            layout.append((prefix + ".bias", (cout,), dict(fan_in=self.temb_dim, is_bias=True)))
-        for prefix, ch in self._qkv:
-            for n in ("to_q", "to_k", "to_v"):
-                layout.append((f"{prefix}.{n}.weight", (ch, ch), dict(fan_in=ch)))
-            for n in ("to_q", "to_k", "to_v"):
-                layout.append((f"{prefix}.{n}.bias", (ch,), dict(fan_in=ch, is_bias=True)))
-        layout.extend(self._decls)
-        offs, total = {}, 0
-        for name, shape, _ in layout:
-            n = int(math.prod(shape))
-            offs[name] = (total, n, shape)
-            total += (n + 3) // 4 * 4           # keep every parameter 16-byte aligned
-        self._layout, self._offs, self.flat_numel = layout, offs, total
-        dev = self._dev
-        self.flat_param = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.flat_grad = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.P: Dict[str, torch.Tensor] = {}
-        self.G: Dict[str, torch.Tensor] = {}
-        for name, shape, _ in layout:
-            off, n, _ = offs[name]
-            parts = name.split(".")
-            holder = _ensure_path(self, parts[:-1])
-            p = nn.Parameter(self.flat_param[off:off + n].view(shape), requires_grad=True)
-            p.grad = self.flat_grad[off:off + n].view(shape)
-            holder.register_parameter(parts[-1], p)
-            self.P[name], self.G[name] = p.data, p.grad
+        head = [(prefix + ".weight", (cout, self.temb_dim), dict(fan_in=self.temb_dim)) for prefix, cout in self._temb]
+        head += [(prefix + ".bias", (cout,), dict(fan_in=self.temb_dim, is_bias=True)) for prefix, cout in self._temb]
+        super()._materialise(head, grads=True)
+        layout, offs, total, dev = self._layout, self._offs, self.flat_numel, self._dev
         # fused views
         n_t = sum(c for _, c in self._temb)
         o0 = offs[self._temb[0][0] + ".weight"][0]
@@ -853,12 +801,6 @@ class UNet2DModel(nn.Module):
         self.bt_all = self.flat_param[ob:ob + n_t]
         self.gWt_all = self.flat_grad[o0:o0 + n_t * self.temb_dim].view(n_t, self.temb_dim)
         self.gbt_all = self.flat_grad[ob:ob + n_t]
-        self.Pq, self.Gq = {}, {}
-        for prefix, ch in self._qkv:
-            ow, obq = offs[f"{prefix}.to_q.weight"][0], offs[f"{prefix}.to_q.bias"][0]
-            for src, dst in ((self.flat_param, self.Pq), (self.flat_grad, self.Gq)):
-                dst[prefix + "::qkv_w"] = src[ow:ow + 3 * ch * ch].view(3 * ch, ch)
-                dst[prefix + "::qkv_b"] = src[obq:obq + 3 * ch]
         # transposed conv weights for dgrad, refreshed once per backward
         self._wt_offs, wt_total = {}, 0
         for name, shape, _ in layout:
@@ -934,47 +876,9 @@ class UNet2DModel(nn.Module):
         self._packed: Optional[_PackedConvWeights] = None
         self._packed16: Optional[_PackedConvWeights] = None     # f16 operands of the opt-in mixed-precision mode (conv_math = "f16")
         self._wt_fresh = set()
-        self.reset_parameters()
-
-    @torch.no_grad()
-    def reset_parameters(self, seed: Optional[int] = None):
-        """torch default init of Conv2d / Linear (kaiming_uniform(a=sqrt(5)) = U(+-1/sqrt(fan_in))) and GroupNorm."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
-        host = torch.zeros(self.flat_numel, dtype=torch.float32)
-        for name, shape, meta in self._layout:
-            off, n, _ = self._offs[name]
-            if meta.get("ones"):
-                host[off:off + n] = 1.0
-            elif meta.get("zeros"):
-                host[off:off + n] = 0.0
-            else:
-                bound = 1.0 / math.sqrt(meta["fan_in"])
-                host[off:off + n] = (torch.rand(n, generator=gen) * 2 - 1) * bound
-        self.flat_param.copy_(host)
 
     def zero_grad(self, set_to_none: bool = False):          # keeps .grad views into the flat buffer
         ops.scale_(self.flat_grad, 0.0)
-
-    def load_state_dict(self, state_dict, strict: bool = True):
-        sd = {}
-        for k, v in state_dict.items():
-            parts = k.split(".")
-            if "attentions" in parts and len(parts) >= 2 and parts[-2] in LEGACY_ATTN:   # diffusers < 0.17 names
-                parts[-2] = LEGACY_ATTN[parts[-2]]
-                k = ".".join(parts)
-            sd[k] = v
-        missing = [k for k in self._offs if k not in sd]
-        unexpected = [k for k in sd if k not in self._offs]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"load_state_dict: missing {missing[:5]}..., unexpected {unexpected[:5]}...")
-        with torch.no_grad():
-            for k, v in sd.items():
-                if k in self._offs:
-                    off, n, shape = self._offs[k]
-                    assert tuple(v.shape) == tuple(shape) or v.numel() == n, (k, v.shape, shape)
-                    self.flat_param[off:off + n].copy_(v.reshape(-1).to(torch.float32))
-        self.weights_changed()
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
 
     def refresh_packed(self, bwd: bool):
         """Rebuild whatever packed operand sets exist (split-precision, f16) for the current weights -- what a captured graph's caller does before
@@ -990,20 +894,6 @@ class UNet2DModel(nn.Module):
         for pk in (self._packed, self._packed16):
             if pk is not None:
                 pk.key = {False: None, True: None}
-
-    def to(self, *args, **kwargs):          # parameters are views of one flat device buffer: never re-materialise
-        return self
-
-    def cuda(self, device=None):
-        return self
-
-    @property
-    def device(self):
-        return self._dev
-
-    @property
-    def dtype(self):
-        return torch.float32
 
     # ------------------------------------------------------------------------------------------ scratch
     # ---- per-batch partial sums of the bias / GroupNorm-parameter gradients and their deferred reduction ----

@@ -12,43 +12,19 @@ downsample, GroupNorm+SiLU, 1x1 convs, attention GEMMs + column softmax, ``vd_vq
 flat fp32 buffer like the UNet's.
 
 The encoder's input gradient is a launch sequence over the input-gradient halves of ``_Conv.bwd`` / ``_Norm.bwd`` / ``_Attn.bwd``, the way the
-UNet's frozen-weight pass uses them: the network answers their weight-gradient, row-sum, column-sum and pack requests with nothing
-(``_dx_only``), on the current stream.  ``decode`` stays forward-only.
+UNet's frozen-weight pass uses them: the network answers their weight-gradient, row-sum, column-sum and pack requests with nothing, on the
+current stream (the defaults of ``flatnet.FlatParamNet``, which also holds the flat buffer and the switch).  ``decode`` stays forward-only.
 """
 from __future__ import annotations
 
-import contextlib
-import math
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from . import ops
-from .lib import A_COL, B_CONV3, B_CONV3_S2, B_CONV3_UP, B_PLAIN
-from .unet import LEGACY_ATTN, _Attn, _Conv, _Norm, _ensure_path
-
-
-def _conv1x1_dgrad(w2d, dout):
-    """dx = W^T dout of a 1x1 convolution with weights [M, C] (the shortcut's and quant_conv's input gradient)."""
-    M, Cc = w2d.shape
-    B, _, H, W = dout.shape
-    HW = H * W
-    dx = torch.empty((B, Cc, H, W), device=dout.device, dtype=torch.float32)
-    ops.gemm(w2d, dout, dx, M=Cc, N=B * HW, K=M, a_mode=A_COL, b_mode=B_PLAIN, NP=HW, lda=Cc, ldb=HW, b_bstride=ops._img(dout)[4], ldd=HW,
-             d_bstride=Cc * HW)
-    return dx
-
-
-class _NoGrads:
-    """What a frozen network hands `_Conv.bwd` / `_Attn.bwd` where they name a gradient view: nothing is ever written through it."""
-
-    def __getitem__(self, key):
-        return self
-
-    def view(self, *shape):
-        return self
+from .flatnet import FlatParamNet
+from .lib import B_CONV3_S2, B_CONV3_UP
+from .unet import _Attn, _Conv, _Norm, _conv1x1_dgrad
 
 
 class _ResnetNoTemb:
@@ -97,7 +73,7 @@ class _ResnetNoTemb:
         self.norm2.bwd(da2, h1, m2, r2, dh1)
         da1 = da2 if self.cin == self.cout else torch.empty_like(x)
         self.conv1.bwd(dh1, None, da1, skip_bias=True)
-        dsc = _conv1x1_dgrad(self.net.P[self.prefix + ".conv_shortcut.weight"].view(self.cout, self.cin), dout) if self.has_sc else dout
+        dsc = _conv1x1_dgrad(self.net, self.prefix + ".conv_shortcut", self.cout, self.cin, dout) if self.has_sc else dout
         return self.norm1.bwd(da1, x, m1, r1, torch.empty_like(x), extra=dsc)
 
 
@@ -144,7 +120,7 @@ class _VQEncodeFn(torch.autograd.Function):
         return None, net._encode_backward(tape, dlat.contiguous())
 
 
-class VQModel(nn.Module):
+class VQModel(FlatParamNet):
     """Drop-in for diffusers ``VQModel`` on the inference surface the reference uses: ``.encode(x).latents``,
     ``.decode(z).sample``, ``.config``, ``.device``, ``.eval()``, ``.requires_grad_``, ``state_dict``/``load_state_dict``."""
 
@@ -164,14 +140,7 @@ class VQModel(nn.Module):
             latent_channels=latent_channels, sample_size=sample_size, num_vq_embeddings=num_vq_embeddings,
             norm_num_groups=norm_num_groups, vq_embed_dim=vq_embed_dim, scaling_factor=scaling_factor)
         self.groups, self.eps = norm_num_groups, norm_eps
-        if device is not None:
-            self._dev = torch.device(device)
-        elif torch.cuda.is_available():
-            self._dev = torch.device("cuda", torch.cuda.current_device())
-        else:
-            self._dev = torch.device("cpu")       # structure-only use; compute fails loudly in lib.require_device()
-        self._decls: List[Tuple[str, Tuple[int, ...], dict]] = []
-        self._qkv: List[Tuple[str, int]] = []
+        self._begin_declarations(device)
 
         # ---- encoder ----
         self.e_in = _Conv(self, "encoder.conv_in", in_channels, boc[0])
@@ -204,141 +173,6 @@ class VQModel(nn.Module):
         self.d_out = _Conv(self, "decoder.conv_out", ch, out_channels)
         self._materialise()
 
-    # ------------------------------------------------------------------------------------------ parameter plumbing
-    def _decl(self, name, shape, fan_in=None, is_bias=False, ones=False, zeros=False, codebook=False):
-        self._decls.append((name, tuple(shape), dict(fan_in=fan_in, is_bias=is_bias, ones=ones, zeros=zeros, codebook=codebook)))
-
-    def _decl_qkv(self, prefix, ch):
-        self._qkv.append((prefix, ch))
-        return prefix + "::qkv_w", prefix + "::qkv_b"
-
-    def _materialise(self):
-        layout = []
-        for prefix, ch in self._qkv:                 # q, k, v adjacent: one [3C, C] projection per attention block
-            for n in ("to_q", "to_k", "to_v"):
-                layout.append((f"{prefix}.{n}.weight", (ch, ch), dict(fan_in=ch)))
-            for n in ("to_q", "to_k", "to_v"):
-                layout.append((f"{prefix}.{n}.bias", (ch,), dict(fan_in=ch, is_bias=True)))
-        layout.extend(self._decls)
-        offs, total = {}, 0
-        for name, shape, _ in layout:
-            n = int(math.prod(shape))
-            offs[name] = (total, n, shape)
-            total += (n + 3) // 4 * 4
-        self._layout, self._offs, self.flat_numel = layout, offs, total
-        self.flat_param = torch.zeros(total, device=self._dev, dtype=torch.float32)
-        self.P: Dict[str, torch.Tensor] = {}
-        for name, shape, _ in layout:
-            off, n, _ = offs[name]
-            parts = name.split(".")
-            holder = _ensure_path(self, parts[:-1])
-            p = nn.Parameter(self.flat_param[off:off + n].view(shape), requires_grad=False)
-            holder.register_parameter(parts[-1], p)
-            self.P[name] = p.data
-        self.Pq = {}
-        for prefix, ch in self._qkv:
-            ow, ob = offs[f"{prefix}.to_q.weight"][0], offs[f"{prefix}.to_q.bias"][0]
-            self.Pq[prefix + "::qkv_w"] = self.flat_param[ow:ow + 3 * ch * ch].view(3 * ch, ch)
-            self.Pq[prefix + "::qkv_b"] = self.flat_param[ob:ob + 3 * ch]
-        self.reset_parameters()
-
-    @torch.no_grad()
-    def reset_parameters(self, seed: Optional[int] = None):
-        """torch default init of Conv2d / Linear / GroupNorm; codebook U(-1/n_e, 1/n_e) like upstream VectorQuantizer."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
-        host = torch.zeros(self.flat_numel, dtype=torch.float32)
-        for name, shape, meta in self._layout:
-            off, n, _ = self._offs[name]
-            if meta.get("ones"):
-                host[off:off + n] = 1.0
-            elif meta.get("zeros"):
-                host[off:off + n] = 0.0
-            else:
-                bound = 1.0 / shape[0] if meta.get("codebook") else 1.0 / math.sqrt(meta["fan_in"])
-                host[off:off + n] = (torch.rand(n, generator=gen) * 2 - 1) * bound
-        self.flat_param.copy_(host)
-
-    def load_state_dict(self, state_dict, strict: bool = True):
-        sd = {}
-        for k, v in state_dict.items():
-            parts = k.split(".")
-            if "attentions" in parts and len(parts) >= 2 and parts[-2] in LEGACY_ATTN:
-                parts[-2] = LEGACY_ATTN[parts[-2]]
-                k = ".".join(parts)
-            sd[k] = v
-        missing = [k for k in self._offs if k not in sd]
-        unexpected = [k for k in sd if k not in self._offs]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"load_state_dict: missing {missing[:5]}..., unexpected {unexpected[:5]}...")
-        with torch.no_grad():
-            for k, v in sd.items():
-                if k in self._offs:
-                    off, n, shape = self._offs[k]
-                    assert v.numel() == n, (k, v.shape, shape)
-                    self.flat_param[off:off + n].copy_(v.reshape(-1).to(torch.float32))
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
-
-    def to(self, *args, **kwargs):
-        return self
-
-    def cuda(self, device=None):
-        return self
-
-    @property
-    def device(self):
-        return self._dev
-
-    # ------------------------------------------------------------------------------------------ the encoder's input gradient
-    _input_grad = False
-
-    @contextlib.contextmanager
-    def input_gradients(self):
-        """Inside: `encode(x)` of an x that requires grad keeps a tape and returns latents with a grad_fn; `torch.autograd.grad(lat, x, dlat)`
-        is then the encoder's input-gradient pass.  Forward AND backward belong inside.  Whatever the parameters' requires_grad flags say, no
-        parameter gradient is computed or written.  Outside (the default), `encode` is the no-grad forward it always was."""
-        old = self._input_grad
-        self._input_grad = True
-        try:
-            yield self
-        finally:
-            self._input_grad = old
-
-    # What _Conv.bwd / _Norm.bwd / _Attn.bwd ask of their network, answered for a frozen one: no weight gradient, no bias or GroupNorm-parameter
-    # sums, no pack pass, no side stream -- the input-gradient halves on the current stream are all that runs.
-    _dx_only = True
-    G = Gq = _NoGrads()
-
-    def wgrad(self, *args, **kwargs):
-        return None
-
-    def rowsum(self, *args, **kwargs):
-        return None
-
-    def colsum_later(self, *args, **kwargs):
-        return None
-
-    def pack_later(self, t):
-        return None
-
-    def scratch_bc(self, B, Cc, slot=0):
-        """[B * Cc] floats the GroupNorm backward kernel writes its per-image parameter partials into (never reduced here)."""
-        return torch.empty(B * Cc, device=self._dev, dtype=torch.float32)
-
-    def wt_view(self, prefix, M, Cc, T, fresh=True):
-        """Transposed weights [C, M*T] of `prefix` for the stride-1 input gradient; transposed once per state of the weights."""
-        cache = self.__dict__.setdefault("_wt_cache", {})
-        key = (self.flat_param._version, ops.WEIGHTS_EPOCH)
-        ent = cache.get(prefix)
-        if ent is None or ent[0] != key:
-            wt = ent[1] if ent is not None else torch.empty(M * Cc * T, device=self._dev, dtype=torch.float32)
-            ops.weight_transpose(self.P[prefix + ".weight"], wt, M, Cc, T)
-            ent = cache[prefix] = (key, wt)
-        return ent[1].view(Cc, M * T)
-
-    @property
-    def dtype(self):
-        return torch.float32
-
     # ------------------------------------------------------------------------------------------ forward launch sequences
     def _conv1x1(self, name, x):
         w = self.P[name + ".weight"]
@@ -351,8 +185,9 @@ class VQModel(nn.Module):
         return torch.empty((B, ch, int(H * scale), int(W * scale)), device=x.device, dtype=torch.float32)
 
     def encode(self, x: torch.Tensor, return_dict: bool = True):
-        """latents = quant_conv(Encoder(x)); NOT quantised (upstream VQModel.encode).  Differentiable with respect to x inside
-        `input_gradients()` only."""
+        """latents = quant_conv(Encoder(x)); NOT quantised (upstream VQModel.encode).  Inside `input_gradients()` only, an x that requires grad
+        keeps a tape and the latents get a grad_fn: `torch.autograd.grad(lat, x, dlat)` is then the encoder's input-gradient pass.  Whatever the
+        parameters' requires_grad flags say, no parameter gradient is computed or written."""
         if self._input_grad and torch.is_grad_enabled() and x.requires_grad:
             lat = _VQEncodeFn.apply(self, x.to(self._dev, torch.float32).contiguous())
         else:
@@ -385,8 +220,8 @@ class VQModel(nn.Module):
 
     def _encode_backward(self, tape, dlat):
         """dL/dx from dL/dlatents: quant_conv's input gradient, the tape backwards, conv_in's input gradient."""
-        wq = self.P["quant_conv.weight"]
-        g = _conv1x1_dgrad(wq.view(wq.shape[0], wq.shape[1]), dlat)
+        vq_dim, lat_ch = self.P["quant_conv.weight"].shape[:2]
+        g = _conv1x1_dgrad(self, "quant_conv", vq_dim, lat_ch, dlat)
         while tape:
             kind, layer, saved = tape.pop()
             if kind == "conv":                       # conv_out and the padded stride-2 downsamplers: saved is the input's shape
