@@ -14,6 +14,7 @@ runs on the HIP InceptionV3 (villandiffusion_amd/inception.py) and needs the pub
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -39,6 +40,14 @@ MODE_SAMPLING_OPTS = {"project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt
                       "infer_start", "inpaint_mul", "task"}
 MODE_MEASURE_OPTS = MODE_SAMPLING_OPTS
 IGNORE_ARGS = {"overwrite", "is_save_all_model_epochs", "R_trigger_only"}
+# options of this build beyond the reference's: --ema_decay (train modes; resume takes it from args.json), --use_ema (sampling / measure).
+# At their defaults they are left out of the JSON side files, which then read as they did before the options existed.
+EXTRA_MODE_OPTS = {MODE_SAMPLING: {"use_ema"}, MODE_MEASURE: {"use_ema"}}
+EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False}
+
+
+def _side_file(d: dict) -> dict:
+    return {k: v for k, v in d.items() if k != "extra" and not (k in EXTRA_DEFAULTS and v == EXTRA_DEFAULTS[k])}
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -68,6 +77,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     a("--R_trigger_only", "-trigonly", action="store_true"); a("--postfix", "-p", type=str); a("--fclip", "-fc", type=str, choices=["w", "o"])
     a("--save_image_epochs", "-sie", type=int); a("--save_model_epochs", "-sme", type=int)
     a("--is_save_all_model_epochs", "-isame", action="store_true"); a("--sample_ep", "-se", type=int); a("--result", "-res", type=str)
+    # not in the reference: keep an exponential moving average of the weights while training (diffusers EMAModel; absent = off) / sample from it
+    a("--ema_decay", type=float); a("--use_ema", action="store_true")
     return p.parse_args(argv)
 
 
@@ -88,6 +99,7 @@ class TrainingConfig:
     lr_warmup_steps: int = 500; mixed_precision: str = "no"; seed: int = 0; dataset_path: str = "datasets"
     ckpt_dir: str = "ckpt"; data_ckpt_dir: str = "data.ckpt"; ep_model_dir: str = "epochs"
     clip: bool = False; output_dir: str = ""; ckpt_path: Optional[str] = None; data_ckpt_path: Optional[str] = None
+    ema_decay: Optional[float] = None; use_ema: bool = False
     extra: dict = field(default_factory=dict)
 
 
@@ -112,7 +124,7 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
             for k, v in json.load(f).items():
                 if v is not None and hasattr(cfg, k):
                     setattr(cfg, k, v)
-        allowed = {MODE_RESUME: MODE_RESUME_OPTS, MODE_SAMPLING: MODE_SAMPLING_OPTS, MODE_MEASURE: MODE_MEASURE_OPTS}[mode]
+        allowed = {MODE_RESUME: MODE_RESUME_OPTS, MODE_SAMPLING: MODE_SAMPLING_OPTS, MODE_MEASURE: MODE_MEASURE_OPTS}[mode] | EXTRA_MODE_OPTS.get(mode, set())
         for k, v in given.items():
             if k in allowed:
                 setattr(cfg, k, v)
@@ -120,7 +132,7 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
                 raise NotImplementedError(f"Argument: {k}={v} isn't supported in mode: {mode}")
         cfg.output_dir = base
     else:
-        banned = NOT_MODE_TRAIN if mode == MODE_TRAIN else NOT_MODE_TRAIN_MEASURE
+        banned = (NOT_MODE_TRAIN if mode == MODE_TRAIN else NOT_MODE_TRAIN_MEASURE) | {"use_ema"}
         for k, v in given.items():
             if k in banned:
                 raise NotImplementedError(f"Argument: {k}={v} isn't supported in mode: {mode}")
@@ -164,12 +176,12 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
                 raise ValueError(f"Output directory: {cfg.output_dir} has already been created, please set overwrite flag --overwrite or -o")
             os.makedirs(cfg.output_dir, exist_ok=True)
             with open(os.path.join(cfg.output_dir, "args.json"), "w") as f:
-                json.dump({k: v for k, v in vars(args).items()}, f, indent=2)
+                json.dump(_side_file(vars(args)), f, indent=2)
             with open(os.path.join(cfg.output_dir, "config.json"), "w") as f:
-                json.dump({k: v for k, v in vars(cfg).items() if k != "extra"}, f, indent=2)
+                json.dump(_side_file(vars(cfg)), f, indent=2)
     elif mode in (MODE_SAMPLING, MODE_MEASURE) and rank0:              # :303-306 sampling.json / measure.json = the effective config
         with open(os.path.join(cfg.output_dir, f"{mode}.json"), "w") as f:
-            json.dump({k: v for k, v in vars(cfg).items() if k != "extra"}, f, indent=2)
+            json.dump(_side_file(vars(cfg)), f, indent=2)
     cfg.ckpt_path = os.path.join(cfg.output_dir, cfg.ckpt_dir)
     cfg.data_ckpt_path = os.path.join(cfg.output_dir, cfg.data_ckpt_dir)
     if rank0:
@@ -420,9 +432,11 @@ def checkpoint(cfg, trainer, pipeline, epoch, step, dsl=None):
     if dsl is not None and hasattr(dsl, "loader_state"):
         data["loader"] = dsl.loader_state()                           # device flip generator: a resumed run draws the same flips
     torch.save(data, cfg.data_ckpt_path)
-    pipeline.save_pretrained(cfg.output_dir)
+    opt = trainer.opt
+    ema = (opt.ema, opt.ema_cfg, opt.ema_step) if opt.ema is not None else None        # EMA on: unet_ema/ beside unet/
+    pipeline.save_pretrained(cfg.output_dir, ema=ema)
     if cfg.is_save_all_model_epochs:                                   # reference :1110-1114: a copy per checkpointed epoch
-        pipeline.save_pretrained(get_ep_model_path(cfg, cfg.output_dir, epoch))
+        pipeline.save_pretrained(get_ep_model_path(cfg, cfg.output_dir, epoch), ema=ema)
 
 
 def get_ep_model_path(cfg, dir: str, epoch: int) -> str:
@@ -443,7 +457,7 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
     import torch
     from loss import LossFn
     from model import DiffuserModelSched
-    from villandiffusion_amd.trainer import Trainer
+    from villandiffusion_amd.trainer import EMAConfig, Trainer
     if cfg.mode == MODE_RESUME:                                        # the run directory setup() resolved (reference: config.ckpt IS that path)
         src = cfg.output_dir
     else:
@@ -458,7 +472,7 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
                      vp_scale=cfg.vp_scale, ve_scale=cfg.ve_scale)
     n_batch = (len(dsl) + cfg.batch * world - 1) // (cfg.batch * world)
     trainer = Trainer(model, loss_fn, lr=cfg.learning_rate, total_steps=n_batch * cfg.epoch, warmup_steps=cfg.lr_warmup_steps,
-                      grad_accum=cfg.gradient_accumulation_steps)
+                      grad_accum=cfg.gradient_accumulation_steps, ema=EMAConfig(decay=cfg.ema_decay) if cfg.ema_decay is not None else None)
     start_epoch, step = 0, 0
     if cfg.mode == MODE_RESUME:
         trainer.load_state_dict(torch.load(os.path.join(cfg.ckpt_path, "trainer.pt"), map_location=model.device))
@@ -466,6 +480,8 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
         start_epoch, step = int(d["epoch"]), int(d["step"])
         if hasattr(dsl, "load_loader_state"):
             dsl.load_loader_state(d.get("loader"))
+    # EMA on: the grids during and after training show the EMA weights (diffusers' training example: store / copy_to / restore)
+    sampling_weights = trainer.ema_weights if trainer.opt.ema is not None else contextlib.nullcontext
     pipeline = get_pipeline(None, model, vae, noise_sched)
     if rank == 0:
         sampling(cfg, 0, pipeline, dsl)
@@ -483,7 +499,8 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
                 print(f"epoch {epoch} step {step} loss {float(loss):.5f} lr {trainer.lr:.3e}", flush=True)
         if rank == 0:
             if (epoch + 1) % cfg.save_image_epochs == 0 or epoch == cfg.epoch - 1:
-                sampling(cfg, epoch, pipeline, dsl)
+                with sampling_weights():
+                    sampling(cfg, epoch, pipeline, dsl)
                 if dsl.image_size >= 128:                              # the captured forwards pin their peak memory: release it before training resumes
                     from villandiffusion_amd.pipelines import drop_sampler_graphs
                     drop_sampler_graphs(model)
@@ -491,7 +508,8 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
                 checkpoint(cfg, trainer, pipeline, epoch, step, dsl)
     if rank == 0:                                                      # reference :1192-1195
         checkpoint(cfg, trainer, pipeline, epoch, step, dsl)
-        sampling(cfg, "final", pipeline, dsl)
+        with sampling_weights():
+            sampling(cfg, "final", pipeline, dsl)
     return pipeline
 
 
@@ -616,6 +634,9 @@ def main(argv: Optional[List[str]] = None):
             src = get_ep_model_path(cfg, cfg.output_dir, cfg.sample_ep)
         model, vae, noise_sched, get_pipeline = DiffuserModelSched.get_pretrained(ckpt=src, clip_sample=cfg.clip,
                                                                                   noise_sched_type=cfg.sched, sde_type=cfg.sde_type)
+        if cfg.use_ema:                                                # the weights of unet_ema/ instead of unet/
+            from villandiffusion_amd.pipelines import load_ema_weights
+            load_ema_weights(model, DiffuserModelSched._resolve_dir(src) or src)
         pipeline = get_pipeline(None, model, vae, noise_sched)
     if cfg.mode == MODE_SAMPLING and rank == 0:
         sampling(cfg, cfg.sample_ep if cfg.sample_ep is not None else "final", pipeline, dsl)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge: additions only */
+#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap: additions only */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -432,6 +432,15 @@ int vd_l2norm_sq(const float* g, int64_t n, float* partial, float* out_sq, void*
  * NULL): the host reads that counter lazily and refuses to go on (default arithmetic) or halves its loss scale (f16 mode). */
 int vd_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* norm_sq, float max_norm,
                  float inv_scale, float lr, float beta1, float beta2, float eps, int step, unsigned* skipped, void* stream);
+/* vd_adam_step plus, in the same pass, the exponential moving average of the updated parameters (diffusers EMAModel.step):
+ * ema += (p_new - ema) * one_minus_decay, each operation rounded on its own.  p / m / v get the bits vd_adam_step gives them.  A skipped step
+ * (see above) leaves ema untouched as well.  one_minus_decay in [0, 1]; ema: n floats, 16-byte aligned like the rest.  36 B/parameter. */
+int vd_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* norm_sq, float max_norm,
+                     float inv_scale, float lr, float beta1, float beta2, float eps, int step, float one_minus_decay, unsigned* skipped,
+                     void* stream);
+/* a <-> b in place, n floats each, bit for bit (nothing is rounded; NaN payloads survive): 16-byte accesses where both pointers allow, 4-byte
+ * otherwise.  The buffers must not overlap. */
+int vd_swap(float* a, float* b, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10 -- sampler steps (diffusers *Scheduler.step, via pipeline(...) VillanDiffusion.py:579).

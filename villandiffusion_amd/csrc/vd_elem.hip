@@ -158,23 +158,43 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-// torch.nn.utils.clip_grad_norm_ (coef = max_norm/(norm+1e-6), clamped to 1) fused into torch.optim.Adam's update.
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n, const float* __restrict__ norm_sq,
-                                                   float max_norm, float inv_scale, float lr, float beta1, float beta2,
-                                                   float eps, float bc1, float bc2_sqrt, unsigned* __restrict__ skipped) {
-    float gs = inv_scale;
+// One element of torch.optim.Adam's update on the clipped, unscaled gradient g * gs: the arithmetic adam_kernel and adam_ema_kernel share, so that
+// p / m / v come out of both with the same bits.
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float gs, float beta1, float beta2, float eps,
+                                            float step_size, float bc2_sqrt) {
+    const float gr = g * gs;
+    m = m + (gr - m) * (1.f - beta1);          // exp_avg.lerp_(grad, 1-beta1)
+    v = v * beta2 + (1.f - beta2) * gr * gr;   // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = p - step_size * (m / denom);
+}
+
+// The gradient scale of this step -- 1/world, the loss scale and torch.nn.utils.clip_grad_norm_'s coefficient (max_norm/(norm+1e-6), clamped
+// to 1) folded --, or false: the step is skipped.
+// A non-finite gradient (f16 mixed-precision mode: an operand overflowed under the loss scale) skips the whole update, as
+// torch.cuda.amp.GradScaler.step does (reference VillanDiffusion.py:260-264 -> accelerate); the skip is COUNTED (one writer: thread 0 of
+// block 0) so that the host sees every skipped step at its next lazy check, not only the one the check happens to land on
+__device__ __forceinline__ bool adam_grad_scale(const float* __restrict__ norm_sq, float max_norm, float inv_scale,
+                                                unsigned* __restrict__ skipped, float& gs) {
+    gs = inv_scale;
     if (norm_sq) {
-        // a non-finite gradient (f16 mixed-precision mode: an operand overflowed under the loss scale) skips the whole update, as
-        // torch.cuda.amp.GradScaler.step does (reference VillanDiffusion.py:260-264 -> accelerate); the skip is COUNTED (one writer: thread 0 of
-        // block 0) so that the host sees every skipped step at its next lazy check, not only the one the check happens to land on
         if (!(*norm_sq <= 3.0e38f)) {
             if (skipped && blockIdx.x == 0 && threadIdx.x == 0) *skipped += 1u;
-            return;
+            return false;
         }
         const float norm = sqrtf(*norm_sq) * inv_scale;
         gs *= fminf(1.0f, max_norm / (norm + 1e-6f));
     }
+    return true;
+}
+
+// torch.nn.utils.clip_grad_norm_ fused into torch.optim.Adam's update.
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t n, const float* __restrict__ norm_sq,
+                                                   float max_norm, float inv_scale, float lr, float beta1, float beta2,
+                                                   float eps, float bc1, float bc2_sqrt, unsigned* __restrict__ skipped) {
+    float gs;
+    if (!adam_grad_scale(norm_sq, max_norm, inv_scale, skipped, gs)) return;
     const float step_size = lr / bc1;
     const int64_t n4 = n >> 2;
     f32x4* p4 = reinterpret_cast<f32x4*>(p);
@@ -185,23 +205,90 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         f32x4 pv = p4[i], gv = g4[i], mv = m4[i], vv = v4[i];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float gr = gv[j] * gs;
-            mv[j] = mv[j] + (gr - mv[j]) * (1.f - beta1);          // exp_avg.lerp_(grad, 1-beta1)
-            vv[j] = vv[j] * beta2 + (1.f - beta2) * gr * gr;       // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
-            const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-            pv[j] = pv[j] - step_size * (mv[j] / denom);
+            float pj = pv[j], mj = mv[j], vj = vv[j];
+            adam_update(pj, gv[j], mj, vj, gs, beta1, beta2, eps, step_size, bc2_sqrt);
+            pv[j] = pj;
+            mv[j] = mj;
+            vv[j] = vj;
         }
         p4[i] = pv;
         m4[i] = mv;
         v4[i] = vv;
     }
     if (blockIdx.x == 0)
-        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
-            const float gr = g[i] * gs;
-            m[i] = m[i] + (gr - m[i]) * (1.f - beta1);
-            v[i] = v[i] * beta2 + (1.f - beta2) * gr * gr;
-            p[i] = p[i] - step_size * (m[i] / (sqrtf(v[i]) / bc2_sqrt + eps));
+        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) adam_update(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, step_size, bc2_sqrt);
+}
+
+// adam_kernel plus the exponential moving average of the updated parameters in the same pass (diffusers EMAModel.step:
+// shadow.sub_((1 - decay) * (shadow - param)), signs folded: the same bits): ema += (p_new - ema) * one_minus_decay, three individually rounded
+// operations.  A skipped step leaves ema alone too.  5 f32x4 loads + 4 f32x4 stores per item (36 B/parameter; adam_kernel: 28).
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, float* __restrict__ ema, int64_t n,
+                                                       const float* __restrict__ norm_sq, float max_norm, float inv_scale, float lr,
+                                                       float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
+                                                       float one_minus_decay, unsigned* __restrict__ skipped) {
+    float gs;
+    if (!adam_grad_scale(norm_sq, max_norm, inv_scale, skipped, gs)) return;
+    const float step_size = lr / bc1;
+    const int64_t n4 = n >> 2;
+    f32x4* p4 = reinterpret_cast<f32x4*>(p);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    f32x4* m4 = reinterpret_cast<f32x4*>(m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(v);
+    f32x4* e4 = reinterpret_cast<f32x4*>(ema);
+    GRID_STRIDE(i, n4) {
+        f32x4 pv = p4[i], gv = g4[i], mv = m4[i], vv = v4[i], ev = e4[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pj = pv[j], mj = mv[j], vj = vv[j];
+            adam_update(pj, gv[j], mj, vj, gs, beta1, beta2, eps, step_size, bc2_sqrt);
+            pv[j] = pj;
+            mv[j] = mj;
+            vv[j] = vj;
+            ev[j] = add_rn(ev[j], mul_rn(sub_rn(pj, ev[j]), one_minus_decay));
         }
+        p4[i] = pv;
+        m4[i] = mv;
+        v4[i] = vv;
+        e4[i] = ev;
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
+            adam_update(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, step_size, bc2_sqrt);
+            ema[i] = add_rn(ema[i], mul_rn(sub_rn(p[i], ema[i]), one_minus_decay));
+        }
+}
+
+// a <-> b in place: bits move, nothing is rounded (NaN payloads included).  VEC: f32x4 items plus block 0's scalar tail; else scalar throughout.
+template <bool VEC>
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        uint4* a4 = reinterpret_cast<uint4*>(a);
+        uint4* b4 = reinterpret_cast<uint4*>(b);
+        GRID_STRIDE(i, n4) {
+            const uint4 x = a4[i], y = b4[i];
+            a4[i] = y;
+            b4[i] = x;
+        }
+        if (blockIdx.x == 0) {
+            uint32_t* au = reinterpret_cast<uint32_t*>(a);
+            uint32_t* bu = reinterpret_cast<uint32_t*>(b);
+            for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
+                const uint32_t x = au[i], y = bu[i];
+                au[i] = y;
+                bu[i] = x;
+            }
+        }
+    } else {
+        uint32_t* au = reinterpret_cast<uint32_t*>(a);
+        uint32_t* bu = reinterpret_cast<uint32_t*>(b);
+        GRID_STRIDE(i, n) {
+            const uint32_t x = au[i], y = bu[i];
+            au[i] = y;
+            bu[i] = x;
+        }
+    }
 }
 
 // ---- Philox4x32-10 + Box-Muller -------------------------------------------------------------------------------------
@@ -492,6 +579,33 @@ extern "C" int vd_adam_step(float* p, const float* g, float* m, float* v, int64_
     hipLaunchKernelGGL(adam_kernel, dim3(egrid(n, 8)), dim3(256), 0, ST, p, g, m, v, n, norm_sq, max_norm, inv_scale, lr, beta1,
                        beta2, eps, (float)bc1, (float)sqrt(bc2), skipped);
     VD_LAUNCH_CHECK("vd_adam_step");
+    return 0;
+}
+
+extern "C" int vd_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* norm_sq, float max_norm,
+                                float inv_scale, float lr, float beta1, float beta2, float eps, int step, float one_minus_decay,
+                                unsigned* skipped, void* stream) {
+    VD_REQUIRE(p && g && m && v && ema && n > 0 && step >= 1, "vd_adam_ema_step: bad args");
+    VD_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "vd_adam_ema_step: one_minus_decay %g outside [0, 1]", (double)one_minus_decay);
+    VD_REQUIRE(((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)ema)) & 15) == 0, "vd_adam_ema_step: unaligned");
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(egrid(n, 8)), dim3(256), 0, ST, p, g, m, v, ema, n, norm_sq, max_norm, inv_scale, lr, beta1,
+                       beta2, eps, (float)bc1, (float)sqrt(bc2), one_minus_decay, skipped);
+    VD_LAUNCH_CHECK("vd_adam_ema_step");
+    return 0;
+}
+
+extern "C" int vd_swap(float* a, float* b, int64_t n, void* stream) {
+    VD_REQUIRE(a && b && n > 0, "vd_swap: bad args");
+    VD_REQUIRE(((((uintptr_t)a) | ((uintptr_t)b)) & 3) == 0, "vd_swap: pointers not 4-byte aligned");
+    const uintptr_t lo = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)a : (uintptr_t)b, hi = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)b : (uintptr_t)a;
+    VD_REQUIRE(hi - lo >= (uintptr_t)n * 4, "vd_swap: the two buffers overlap");
+    if (((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0)
+        hipLaunchKernelGGL(swap_kernel<true>, dim3(egrid(n, 8)), dim3(256), 0, ST, a, b, n);
+    else
+        hipLaunchKernelGGL(swap_kernel<false>, dim3(egrid(n, 2)), dim3(256), 0, ST, a, b, n);
+    VD_LAUNCH_CHECK("vd_swap");
     return 0;
 }
 

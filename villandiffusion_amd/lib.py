@@ -105,6 +105,8 @@ PROTOTYPES = {
     "vd_image_set_merge": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "vd_l2norm_sq": (_i32, [_vp, _i64, _vp, _vp, _vp]),
     "vd_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
+    "vd_adam_ema_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp]),
+    "vd_swap": (_i32, [_vp, _vp, _i64, _vp]),
     "vd_sched_step": (_i32, [_vp] * 5 + [_i64] + [_f32] * 7 + [C.c_uint64, C.c_uint64, _vp]),
     "vd_batch_l2norm": (_i32, [_vp, _vp, _i32, _i64, _vp]),
     "vd_postprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _vp]),

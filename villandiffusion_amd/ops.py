@@ -1124,6 +1124,26 @@ def adam_step(p, g, m, v, norm_sq, max_norm, inv_scale, lr, beta1, beta2, eps, s
                             eps, step, _p(skipped), _s()), "vd_adam_step"))
 
 
+def adam_ema_step(p, g, m, v, ema, norm_sq, max_norm, inv_scale, lr, beta1, beta2, eps, step, one_minus_decay, skipped=None, weights=True):
+    """adam_step and, in the same launch, ema += (p_new - ema) * one_minus_decay (every operation rounded on its own); a step the kernel skips
+    leaves `ema` alone too.  p / m / v get the bits adam_step gives them."""
+    global WEIGHTS_EPOCH
+    assert ema.is_contiguous() and ema.dtype == torch.float32 and ema.numel() == p.numel()
+    if weights:
+        WEIGHTS_EPOCH += 1
+    _timed("adam_ema_step (adam_ema_kernel)", 36.0 * p.numel(), "hbm", lambda: L.check(      # p, g, m, v, ema read; p, m, v, ema written
+        _lib().vd_adam_ema_step(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(norm_sq), max_norm, inv_scale, lr, beta1, beta2,
+                                eps, step, one_minus_decay, _p(skipped), _s()), "vd_adam_ema_step"))
+
+
+def swap(a, b):
+    """a <-> b in place, bit for bit (vd_swap).  A raw-pointer write: it bumps neither a tensor's version counter nor WEIGHTS_EPOCH -- whoever swaps
+    network weights calls the network's weights_changed() afterwards."""
+    assert a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype == torch.float32 and a.numel() == b.numel()
+    _timed("swap (swap_kernel)", 16.0 * a.numel(), "hbm", lambda: L.check(                   # both read, both written
+        _lib().vd_swap(_p(a), _p(b), a.numel(), _s()), "vd_swap"))
+
+
 # --------------------------------------------------------------------------------------------- samplers / data
 def sched_step(x, eps, out, *, c_eps, c_div, clip, c_x0, c_x, c_e, c_z, z=None, x0_out=None, seed=0, offset=0):
     assert x.is_contiguous() and eps.is_contiguous() and out.is_contiguous()

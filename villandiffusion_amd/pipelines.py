@@ -98,12 +98,35 @@ def sampler_forward(unet, batch, slot: int = 0):
 
 
 MAX_CACHED_GRAPHS = 4
+# what unet_ema/config.json holds beyond the network's own configuration (diffusers EMAModel.save_pretrained's names)
+EMA_CONFIG_KEYS = ("decay", "min_decay", "optimization_step", "update_after_step", "use_ema_warmup", "inv_gamma", "power")
 
 
 def drop_sampler_graphs(unet):
     """Release the captured forwards (and the memory pools they pin) -- called when training resumes after a periodic sampling() pass:
     for the 256x256 models the pinned forward peak can otherwise make the next training step run out of memory."""
     unet.__dict__.pop("_fwd_graphs", None)
+
+
+def _read_unet_weights(path: str, sub: str = "unet"):
+    st = os.path.join(path, sub, "diffusion_pytorch_model.safetensors")
+    if os.path.exists(st):
+        from safetensors.torch import load_file
+        return load_file(st)
+    return torch.load(os.path.join(path, sub, "diffusion_pytorch_model.bin"), map_location="cpu")
+
+
+def _require_ema_folder(path: str):
+    if not os.path.isdir(os.path.join(path, "unet_ema")):
+        raise FileNotFoundError(f"{path}: the EMA weights were asked for, but there is no unet_ema/ folder (the run kept no EMA: "
+                                f"train with --ema_decay, or load without use_ema)")
+
+
+def load_ema_weights(unet, path: str):
+    """Replace the weights of `unet` (loaded from the checkpoint directory `path`) by those of its `unet_ema/` folder."""
+    _require_ema_folder(path)
+    unet.load_state_dict(_read_unet_weights(path, "unet_ema"))
+    return unet
 
 
 class DiffusionPipeline:
@@ -273,7 +296,9 @@ class DiffusionPipeline:
         return chunk * 2 * n_steps * ((numel + 3) // 4)
 
     # ---- diffusers on-disk layout ----
-    def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = True, ema=None):
+        """ema: (flat shadow, trainer.EMAConfig, ema_step) -- additionally writes `unet_ema/` beside `unet/`: the same two files with the weights
+        taken from the shadow, its config.json extended by the EMA state under diffusers' EMAModel names.  Everything else is written as without."""
         os.makedirs(os.path.join(save_directory, "unet"), exist_ok=True)
         os.makedirs(os.path.join(save_directory, "scheduler"), exist_ok=True)
         index = {"_class_name": self._class_name, "_diffusers_version": "0.16.1",
@@ -303,16 +328,36 @@ class DiffusionPipeline:
             save_file(sd, os.path.join(save_directory, "unet", "diffusion_pytorch_model.safetensors"))
         else:
             torch.save(sd, os.path.join(save_directory, "unet", "diffusion_pytorch_model.bin"))
+        if ema is not None:
+            shadow, ecfg, ema_step = ema
+            host = shadow.detach().cpu().reshape(-1)
+            assert host.numel() == self.unet.flat_numel, (host.numel(), self.unet.flat_numel)
+            os.makedirs(os.path.join(save_directory, "unet_ema"), exist_ok=True)
+            with open(os.path.join(save_directory, "unet_ema", "config.json"), "w") as f:
+                json.dump({**cfg, "decay": ecfg.decay, "min_decay": ecfg.min_decay, "optimization_step": int(ema_step),
+                           "update_after_step": ecfg.update_after_step, "use_ema_warmup": ecfg.use_ema_warmup, "inv_gamma": ecfg.inv_gamma,
+                           "power": ecfg.power}, f, indent=2)
+            esd = {}
+            for k, v in sd.items():                      # the names and order of unet/; every parameter is a slice of the flat buffer
+                off, n, shape = self.unet._offs[k]
+                esd[k] = host[off:off + n].view(shape).clone()
+            if safe_serialization:
+                save_file(esd, os.path.join(save_directory, "unet_ema", "diffusion_pytorch_model.safetensors"))
+            else:
+                torch.save(esd, os.path.join(save_directory, "unet_ema", "diffusion_pytorch_model.bin"))
         with open(os.path.join(save_directory, "scheduler", "scheduler_config.json"), "w") as f:
             json.dump({k: v for k, v in self.scheduler.scheduler_config().items() if v is None or isinstance(v, (int, float, str, bool, list))},
                       f, indent=2)
 
     @classmethod
-    def from_pretrained(cls, path: str, **kwargs):
+    def from_pretrained(cls, path: str, use_ema: bool = False, **kwargs):
+        """use_ema: the network takes the weights of `unet_ema/` (written by save_pretrained(..., ema=...)) instead of `unet/`."""
         if not os.path.isdir(path):
             raise FileNotFoundError(
                 f"{path}: not a local diffusers checkpoint directory (hub ids such as 'google/ddpm-cifar10-32' need a "
                 f"network/HF cache; download the repo and pass its directory)")
+        if use_ema:
+            _require_ema_folder(path)
         with open(os.path.join(path, "unet", "config.json")) as f:
             cfg = json.load(f)
         cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
@@ -321,13 +366,10 @@ class DiffusionPipeline:
             unet = NCSNppModel(**cfg)
         else:
             unet = UNet2DModel(**cfg)
-        st = os.path.join(path, "unet", "diffusion_pytorch_model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
+        if use_ema:
+            load_ema_weights(unet, path)                  # (the one reader of unet_ema/: the driver's --use_ema calls it too)
         else:
-            sd = torch.load(os.path.join(path, "unet", "diffusion_pytorch_model.bin"), map_location="cpu")
-        unet.load_state_dict(sd)
+            unet.load_state_dict(_read_unet_weights(path))
         with open(os.path.join(path, "scheduler", "scheduler_config.json")) as f:
             scfg = json.load(f)
         name = scfg.pop("_class_name", "DDPMScheduler")

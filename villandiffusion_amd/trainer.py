@@ -11,7 +11,10 @@ plus the accelerate semantics of SURVEY Appendix B), one process per GPU.
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes
 import math
+from dataclasses import asdict, dataclass
 from typing import Callable, Dict, Optional
 
 import torch
@@ -21,12 +24,44 @@ from . import ops
 from .schedulers import get_cosine_schedule_with_warmup_lambda
 
 
+@dataclass
+class EMAConfig:
+    """The exponential moving average of the weights, with the parameters (and defaults) of diffusers' ``EMAModel``."""
+    decay: float = 0.9999
+    min_decay: float = 0.0
+    update_after_step: int = 0
+    use_ema_warmup: bool = False
+    inv_gamma: float = 1.0
+    power: float = 2 / 3
+
+
+def ema_decay_at(k: int, cfg: EMAConfig) -> float:
+    """diffusers ``EMAModel.get_decay`` for the k-th EMA update (k counts updates, the current one included), in Python doubles:
+    n = max(0, k - update_after_step - 1); n <= 0 gives 0 (the shadow takes the parameters as they are); else (1 + n) / (10 + n), or
+    1 - (1 + n / inv_gamma) ** -power with warm-up, clamped to [min_decay, decay]."""
+    n = max(0, int(k) - int(cfg.update_after_step) - 1)
+    if n <= 0:
+        return 0.0
+    d = 1.0 - (1.0 + n / cfg.inv_gamma) ** -cfg.power if cfg.use_ema_warmup else (1.0 + n) / (10.0 + n)
+    return max(min(d, float(cfg.decay)), float(cfg.min_decay))
+
+
+def ema_one_minus_decay(k: int, cfg: EMAConfig) -> float:
+    """1 - ema_decay_at(k, cfg) as the C float the kernel receives."""
+    return ctypes.c_float(1.0 - ema_decay_at(k, cfg)).value
+
+
 class FusedAdam:
     """torch.optim.Adam(betas=(0.9, 0.999), eps=1e-8, weight_decay=0) on one flat buffer, with the global-norm clip
-    fused in.  ``state_dict`` is flat too (exp_avg / exp_avg_sq / step)."""
+    fused in.  ``state_dict`` is flat too (exp_avg / exp_avg_sq / step).  With an ``EMAConfig`` the same launch keeps ``self.ema``, the
+    exponential moving average of the parameters (a copy of them at construction), and ``self.ema_step`` counts its updates."""
 
-    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = 1.0):
+    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = 1.0,
+                 ema: Optional[EMAConfig] = None):
         self.model = model
+        self.ema_cfg = ema
+        self.ema = model.flat_param.detach().clone() if ema is not None else None
+        self.ema_step = 0
         self.lr, self.betas, self.eps, self.max_grad_norm = lr, betas, eps, max_grad_norm
         self.exp_avg = torch.zeros_like(model.flat_param)
         self.exp_avg_sq = torch.zeros_like(model.flat_param)
@@ -43,22 +78,41 @@ class FusedAdam:
         if self.max_grad_norm is not None or need_norm:          # need_norm: the overflow guard of the f16 mode reads it (no clipping: max_norm = inf)
             ops.l2norm_sq(m.flat_grad, self._partial, self.grad_norm_sq)
             nsq = self.grad_norm_sq
-        ops.adam_step(m.flat_param, m.flat_grad, self.exp_avg, self.exp_avg_sq, nsq,
-                      float(self.max_grad_norm if self.max_grad_norm is not None else 3.0e38), grad_inv_scale, self.lr if lr is None else lr, self.betas[0],
-                      self.betas[1], self.eps, self.step_count, skipped=self.skipped if nsq is not None else None)
+        max_norm = float(self.max_grad_norm if self.max_grad_norm is not None else 3.0e38)
+        if self.ema is None:
+            ops.adam_step(m.flat_param, m.flat_grad, self.exp_avg, self.exp_avg_sq, nsq, max_norm, grad_inv_scale, self.lr if lr is None else lr,
+                          self.betas[0], self.betas[1], self.eps, self.step_count, skipped=self.skipped if nsq is not None else None)
+            return
+        # a step the kernel skips leaves the shadow alone; Trainer.check_skipped takes it back out of ema_step, as out of step_count
+        self.ema_step += 1
+        ops.adam_ema_step(m.flat_param, m.flat_grad, self.exp_avg, self.exp_avg_sq, self.ema, nsq, max_norm, grad_inv_scale,
+                          self.lr if lr is None else lr, self.betas[0], self.betas[1], self.eps, self.step_count,
+                          ema_one_minus_decay(self.ema_step, self.ema_cfg), skipped=self.skipped if nsq is not None else None)
 
     def grad_norm(self, grad_inv_scale: float = 1.0) -> float:
         """Global L2 norm of the (averaged) gradient of the last step -- synchronises; for logging/tests only."""
         return math.sqrt(float(self.grad_norm_sq)) * grad_inv_scale
 
     def state_dict(self) -> Dict:
-        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step_count, "lr": self.lr}
+        sd = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step_count, "lr": self.lr}
+        if self.ema is not None:
+            sd.update(ema=self.ema, ema_step=self.ema_step, ema_config=asdict(self.ema_cfg))
+        return sd
 
     def load_state_dict(self, sd: Dict):
+        """A state without a shadow loads into an optimiser without EMA, one with a shadow (its counter, its configuration) into an optimiser
+        with EMA; either mismatch raises: the shadow cannot be made up, and dropping one silently would lose it at the next checkpoint."""
+        if ("ema" in sd) != (self.ema is not None):
+            raise ValueError("load_state_dict: the state " + ("holds" if "ema" in sd else "holds no") + " EMA shadow but this optimiser was built "
+                             + ("without" if "ema" in sd else "with") + " EMA (FusedAdam / Trainer ema=...)")
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.step_count = int(sd["step"])
         self.lr = float(sd.get("lr", self.lr))
+        if self.ema is not None:
+            self.ema.copy_(sd["ema"])
+            self.ema_step = int(sd["ema_step"])
+            self.ema_cfg = EMAConfig(**sd["ema_config"])
 
 
 def allreduce_flat_grad(flat_grad: torch.Tensor, n_buckets: int = 4, even_alone: bool = False):
@@ -178,10 +232,11 @@ class GraphedMicroStep:
 class Trainer:
     def __init__(self, model, loss_fn, lr: float, total_steps: int, warmup_steps: int = 500, grad_accum: int = 1,
                  max_grad_norm: Optional[float] = 1.0, n_allreduce_buckets: int = 4, graph_micro_step: Optional[bool] = None,
-                 force_ddp_path: bool = False):
+                 force_ddp_path: bool = False, ema: Optional[EMAConfig] = None):
         self.model, self.loss_fn = model, loss_fn
         self.base_lr = lr
-        self.opt = FusedAdam(model, lr, max_grad_norm=max_grad_norm)
+        self.opt = FusedAdam(model, lr, max_grad_norm=max_grad_norm, ema=ema)
+        self._ema_swapped = False
         self.lr_lambda: Callable[[int], float] = get_cosine_schedule_with_warmup_lambda(warmup_steps, total_steps)
         self.grad_accum = max(1, int(grad_accum))
         self.micro = 0
@@ -255,6 +310,8 @@ class Trainer:
             self._since_growth = 0
             self.opt.step_count = max(0, self.opt.step_count - new)
             self.sched_step = max(0, self.sched_step - new)
+            if self.opt.ema is not None:                 # the kernel left the shadow alone on those steps: they are no EMA updates either
+                self.opt.ema_step = max(0, self.opt.ema_step - new)
         elif count_step and self._scale() != 1.0 and self._since_growth >= self.scale_growth_every:
             self.loss_scale = min(float(2 ** 24), self.loss_scale * 2.0)
             self._since_growth = 0
@@ -265,9 +322,38 @@ class Trainer:
     def lr(self) -> float:
         return self.base_lr * self.lr_lambda(self.sched_step)
 
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """While open, the network holds the EMA weights and ``opt.ema`` the raw ones (diffusers' ``store`` / ``copy_to`` / ``restore``): the two
+        flat buffers are exchanged in place on entry and again on exit, also after an exception -- no third buffer, no rounding.  The swap writes
+        through raw pointers, which no version counter sees, so the operands derived from the weights are dropped each time
+        (``model.weights_changed()``); the captured sampler forwards read ``flat_param`` by address and rebuild the packed operands before each
+        replay, so they follow without a new capture.  It does not nest, and it cannot be entered inside an accumulation window (the gradients
+        accumulated so far belong to the raw weights).  No optimiser step belongs inside."""
+        if self.opt.ema is None:
+            raise RuntimeError("ema_weights(): this trainer keeps no EMA (construct it with ema=EMAConfig(...))")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() does not nest: the network already holds the EMA weights")
+        if self.micro % self.grad_accum != 0:
+            raise RuntimeError(f"ema_weights() inside an open accumulation window (micro-step {self.micro % self.grad_accum} of {self.grad_accum})")
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self.model
+        finally:
+            self._swap_ema()
+            self._ema_swapped = False
+
+    def _swap_ema(self):
+        ops.swap(self.model.flat_param, self.opt.ema)
+        ops.WEIGHTS_EPOCH += 1                           # caches keyed on (flat_param._version, WEIGHTS_EPOCH): transposed weights, packed operands
+        self.model.weights_changed()
+
     def train_step(self, batch, timesteps: torch.Tensor, noise: Optional[torch.Tensor] = None, last_batch: bool = False,
                    target_key: str = "target", poison_key: str = "pixel_values"):
         """One micro-step; returns the (un-divided) loss tensor of this micro-batch."""
+        if self._ema_swapped:
+            raise RuntimeError("train_step() inside ema_weights(): the network holds the EMA weights")
         sync = (self.micro + 1) % self.grad_accum == 0 or last_batch   # accelerate: sync on every G-th and on the last batch
         self._sync_now = sync and self.model.bucket_ready_hook is not None
         if self.micro % self.grad_accum == 0:                          # first micro-step of an accumulation window (the scale never changes inside one)
@@ -315,6 +401,8 @@ class Trainer:
         return g(x0, R, noise.to(dev), timesteps.to(dev))
 
     def state_dict(self) -> Dict:
+        if self._ema_swapped:
+            raise RuntimeError("state_dict() inside ema_weights(): the network holds the EMA weights and the shadow the raw ones")
         if getattr(self.model, "device", torch.device("cpu")).type == "cuda":
             self.check_skipped(force=True, count_step=False)      # a checkpoint never records steps the kernel refused
         return {"optimizer": self.opt.state_dict(), "micro": self.micro, "sched_step": self.sched_step,
