@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap: additions only */
+#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step: additions only */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -422,6 +422,28 @@ int vd_score_inv_objective(const float* s, const float* tau, float sigma, float 
  * pointers allow, with the same sums either way.  partial: >= 2048 floats, 8-byte aligned. */
 int vd_image_set_merge(float* mean_a, float* stats_a, int64_t n_a, const float* mean_b, const float* stats_b, int64_t n_b, int64_t chw,
                        float* partial, void* stream);
+/* Adversarial Neuron Pruning (anp.py).  All three take a NEURON TABLE: a device array of n_jobs x 6 int64, one job per selected weight tensor of a
+ * flat parameter buffer, {weight offset in floats, rows, row length, bias offset in floats or -1, index of the layer's first neuron, first
+ * workgroup}; a job owns ceil(rows / 4) workgroups (one 64-lane wave per row), first workgroups ascend from 0 and total_blocks is their sum.  One
+ * launch serves the whole network.  A neuron is a row; neuron j of a job is element (first neuron + j) of mask / delta / xi / gmask / gxi.  Rows
+ * need not be 16-byte aligned: an aligned row moves as f32x4, any other as scalars, with the same values and the same sums either way.
+ *
+ * vd_neuron_scale: w[row j] = s_j * w0[row j] with s_j = mask[j] + delta[j] in f32 (delta NULL: s_j = mask[j]); where the job has a bias,
+ * w[bias j] = (1 + xi[j]) * w0[bias j] (xi NULL: the bias is copied).  Floats of w outside every job are not written.  w != w0. */
+int vd_neuron_scale(const float* w0, float* w, const int64_t* table, int n_jobs, int64_t total_blocks, const float* mask, const float* delta,
+                    const float* xi, void* stream);
+/* gmask[j] (+)= scale * sum_k g[row j][k] * w0[row j][k] and, where the job has a bias, gxi[j] (+)= scale * (g[bias j] * w0[bias j]) (a job
+ * without one leaves its gxi slots untouched; gxi may be NULL).  accumulate != 0 adds to what is there.  With element k of a row in item k / 4,
+ * a lane keeps one f32 partial per position k % 4 over its items q = lane, lane + 64, ... in that order, adds them as (a0 + a1) + (a2 + a3), and
+ * the 64 lanes are added by a fixed xor tree: bit-reproducible, and the longest chain of additions is ceil(len / 256) + 8. */
+int vd_neuron_grad(const float* g, const float* w0, const int64_t* table, int n_jobs, int64_t total_blocks, float* gmask, float* gxi, float scale,
+                   int accumulate, void* stream);
+/* The projected step of the mask and of the perturbations, n floats, every f32 operation rounded on its own, in this order:
+ *   buf given:  d = momentum * buf + g;  buf = d        (torch: buf.mul_(momentum).add_(g))
+ *   buf NULL:   d = use_sign ? (g > 0) - (g < 0) : g    (torch.sign: 0 for +-0)
+ *   x = min(max(x - lr * d, lo), hi)                    (torch: (x - lr * d).clamp(lo, hi), lr an f32)
+ * A negative lr ascends. */
+int vd_neuron_step(float* x, const float* g, float* buf, int64_t n, float lr, float momentum, float lo, float hi, int use_sign, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K9 -- global grad-norm clip + Adam on flat buffers (VillanDiffusion.py:445,1165-1169).

@@ -1,10 +1,11 @@
 // Backdoor mitigation (villandiffusion_amd/mitigation.py): the statistics of a sampled image set (Elijah's uniformity / total-variation features)
-// and the data-free removal loss with its gradient.  Both are HBM-bound reductions with sums in a fixed order (no atomics): a repeat is
-// bit-identical.  Compiled without FMA contraction: the post-processing rounds every operation on its own, as vd_postprocess does.
+// and the data-free removal loss with its gradient; after them the three kernels of Adversarial Neuron Pruning (villandiffusion_amd/anp.py).
+// All are HBM-bound, the reductions with sums in a fixed order (no atomics): a repeat is bit-identical.  Compiled without FMA contraction: the
+// post-processing rounds every operation on its own, as vd_postprocess does, and the neuron kernels restate short torch op sequences.
 //
-// Both kernels walk their elements in ITEMS of four consecutive floats.  Where rows and pointers are 16-byte aligned an item is one f32x4 access,
-// otherwise four scalar ones; which elements a thread owns and the order it adds them in do not depend on that choice, so a strided or unaligned
-// view gives the same bits as its contiguous copy.
+// The removal-loss and image-set kernels walk their elements in ITEMS of four consecutive floats.  Where rows and pointers are 16-byte aligned an
+// item is one f32x4 access, otherwise four scalar ones; which elements a thread owns and the order it adds them in do not depend on that choice, so
+// a strided or unaligned view gives the same bits as its contiguous copy.
 #include "vd_common.h"
 
 namespace {
@@ -15,7 +16,7 @@ inline int item_grid(int64_t items) {
     int64_t g = (items + 255) / 256;
     return (int)(g < 1 ? 1 : (g > MAXP ? MAXP : g));
 }
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+__host__ __device__ inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 #define ITEM_STRIDE(q, n) \
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < (n); q += (int64_t)gridDim.x * blockDim.x)
@@ -296,6 +297,115 @@ __global__ __launch_bounds__(256) void score_inv_grad_kernel(const float* __rest
     }
 }
 
+
+// ---- Adversarial Neuron Pruning (anp.py): neuron-scaled weights, mask gradients and the projected step -------------------------------------------
+// A NEURON TABLE has one job of six int64 per selected weight tensor: {weight offset in floats, rows, row length, bias offset or -1, index of the
+// layer's first neuron, first workgroup}.  A workgroup is four waves and a wave owns one row: workgroup b of a job holds rows [4b, 4b + 4).  A row
+// is walked in ITEMS of four consecutive floats counted from the row's start; item q belongs to lane q % 64.  Where the row's start is 16-byte
+// aligned in every buffer a whole item is one f32x4 access, otherwise (conv_in's 27-float rows, a base pointer off alignment) four scalar ones:
+// which lane owns an element and the order it is used in do not depend on that choice.
+constexpr int NJ = 6;
+
+__device__ __forceinline__ const int64_t* neuron_job(const int64_t* __restrict__ table, int n_jobs) {
+    int lo = 0, hi = n_jobs - 1;
+    const int64_t blk = blockIdx.x;
+    while (lo < hi) {                                            // last job whose first workgroup <= blk (block-uniform)
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[(int64_t)NJ * mid + 5] <= blk) lo = mid; else hi = mid - 1;
+    }
+    return table + (int64_t)NJ * lo;
+}
+
+__global__ __launch_bounds__(256) void neuron_scale_kernel(const float* __restrict__ w0, float* __restrict__ w, const int64_t* __restrict__ table,
+                                                            int n_jobs, const float* __restrict__ mask, const float* __restrict__ delta,
+                                                            const float* __restrict__ xi) {
+    const int64_t* __restrict__ t = neuron_job(table, n_jobs);
+    const int64_t rows = t[1], len = t[2], boff = t[3];
+    const int64_t row = (blockIdx.x - t[5]) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t j = t[4] + row;
+    float s = mask[j];
+    if (delta) s = s + delta[j];
+    const float* __restrict__ src = w0 + t[0] + row * len;
+    float* __restrict__ dst = w + t[0] + row * len;
+    const bool vec = aligned16(src) && aligned16(dst);
+    const int64_t items = (len + 3) >> 2;
+    for (int64_t q = lane; q < items; q += 64) {
+        const int64_t k0 = q << 2;
+        if (vec && k0 + 4 <= len) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(src + k0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = s * v[e];
+            *reinterpret_cast<f32x4*>(dst + k0) = v;
+        } else {
+            for (int e = 0; e < 4 && k0 + e < len; ++e) dst[k0 + e] = s * src[k0 + e];
+        }
+    }
+    if (lane == 0 && boff >= 0) {
+        const float b = w0[boff + row];
+        w[boff + row] = xi ? (1.0f + xi[j]) * b : b;
+    }
+}
+
+// One wave per row.  A lane keeps one partial sum per position e of its items (four chains of ceil(items / 64) products each, items in index order),
+// adds them as (a0 + a1) + (a2 + a3), and the 64 lanes are added by the xor tree of wave_sum: a fixed order, and no chain longer than
+// len / 256 + 8 additions.
+__global__ __launch_bounds__(256) void neuron_grad_kernel(const float* __restrict__ g, const float* __restrict__ w0, const int64_t* __restrict__ table,
+                                                           int n_jobs, float* __restrict__ gmask, float* __restrict__ gxi, float scale,
+                                                           int accumulate) {
+    const int64_t* __restrict__ t = neuron_job(table, n_jobs);
+    const int64_t rows = t[1], len = t[2], boff = t[3];
+    const int64_t row = (blockIdx.x - t[5]) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                     // wave-uniform: the shuffles below see whole waves
+    const int lane = threadIdx.x & 63;
+    const int64_t j = t[4] + row;
+    const float* __restrict__ a = g + t[0] + row * len;
+    const float* __restrict__ b = w0 + t[0] + row * len;
+    const bool vec = aligned16(a) && aligned16(b);
+    const int64_t items = (len + 3) >> 2;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int64_t q = lane; q < items; q += 64) {
+        const int64_t k0 = q << 2;
+        if (vec && k0 + 4 <= len) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(a + k0);
+            const f32x4 y = *reinterpret_cast<const f32x4*>(b + k0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] += x[e] * y[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (k0 + e < len) acc[e] += a[k0 + e] * b[k0 + e];
+        }
+    }
+    const float sum = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    if (lane == 0) {
+        const float v = scale * sum;
+        gmask[j] = accumulate ? gmask[j] + v : v;
+        if (gxi && boff >= 0) {
+            const float u = scale * (g[boff + row] * w0[boff + row]);
+            gxi[j] = accumulate ? gxi[j] + u : u;
+        }
+    }
+}
+
+// x = min(max(x - lr * d, lo), hi), every operation rounded on its own; d = the momentum buffer after buf = momentum * buf + g, or g, or
+// sign(g) = (g > 0) - (g < 0) (0 for +-0 and NaN).
+__global__ __launch_bounds__(256) void neuron_step_kernel(float* __restrict__ x, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
+                                                           float lr, float momentum, float lo, float hi, int use_sign) {
+    ITEM_STRIDE(i, n) {
+        float d = g[i];
+        if (buf) {
+            d = momentum * buf[i] + d;
+            buf[i] = d;
+        } else if (use_sign) {
+            d = (float)(d > 0.f) - (float)(d < 0.f);
+        }
+        x[i] = fminf(fmaxf(x[i] - lr * d, lo), hi);
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -365,5 +475,30 @@ extern "C" int vd_image_set_merge(float* mean_a, float* stats_a, int64_t n_a, co
         hipLaunchKernelGGL(image_set_merge_kernel<false>, dim3(grid), dim3(256), 0, ST, mean_a, mean_b, pd, chw, wb, copy);
     hipLaunchKernelGGL(image_set_merge_finish_kernel, dim3(1), dim3(256), 0, ST, pd, grid, between, stats_a, stats_b, copy);
     VD_LAUNCH_CHECK("vd_image_set_merge");
+    return 0;
+}
+
+extern "C" int vd_neuron_scale(const float* w0, float* w, const int64_t* table, int n_jobs, int64_t total_blocks, const float* mask,
+                               const float* delta, const float* xi, void* stream) {
+    VD_REQUIRE(w0 && w && table && mask && n_jobs > 0 && total_blocks > 0 && total_blocks < (1ll << 31), "vd_neuron_scale: bad args");
+    VD_REQUIRE(w0 != w, "vd_neuron_scale: w must not be w0 (the base weights are read for every pass)");
+    hipLaunchKernelGGL(neuron_scale_kernel, dim3((unsigned)total_blocks), dim3(256), 0, ST, w0, w, table, n_jobs, mask, delta, xi);
+    VD_LAUNCH_CHECK("vd_neuron_scale");
+    return 0;
+}
+
+extern "C" int vd_neuron_grad(const float* g, const float* w0, const int64_t* table, int n_jobs, int64_t total_blocks, float* gmask, float* gxi,
+                              float scale, int accumulate, void* stream) {
+    VD_REQUIRE(g && w0 && table && gmask && n_jobs > 0 && total_blocks > 0 && total_blocks < (1ll << 31), "vd_neuron_grad: bad args");
+    hipLaunchKernelGGL(neuron_grad_kernel, dim3((unsigned)total_blocks), dim3(256), 0, ST, g, w0, table, n_jobs, gmask, gxi, scale, accumulate);
+    VD_LAUNCH_CHECK("vd_neuron_grad");
+    return 0;
+}
+
+extern "C" int vd_neuron_step(float* x, const float* g, float* buf, int64_t n, float lr, float momentum, float lo, float hi, int use_sign,
+                              void* stream) {
+    VD_REQUIRE(x && g && n > 0 && lo <= hi, "vd_neuron_step: bad args");
+    hipLaunchKernelGGL(neuron_step_kernel, dim3(item_grid(n)), dim3(256), 0, ST, x, g, buf, n, lr, momentum, lo, hi, use_sign);
+    VD_LAUNCH_CHECK("vd_neuron_step");
     return 0;
 }

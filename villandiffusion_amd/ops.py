@@ -1107,6 +1107,51 @@ def image_set_merge(mean_a, stats_a, n_a, mean_b, stats_b, n_b, partial):
     return stats_a
 
 
+def _neuron_args(tab, flat, *per_neuron):
+    """tab: anp.NeuronTable, resident on flat's device.  Every offset of its jobs is checked against the flat buffer here, on the host: the kernels
+    trust the table."""
+    assert flat.is_contiguous() and flat.dtype == torch.float32 and flat.numel() >= tab.extent, (flat.numel(), tab.extent)
+    for v in per_neuron:
+        assert v is None or (v.is_contiguous() and v.dtype == torch.float32 and v.numel() == tab.n_neurons), "one f32 per neuron"
+    return tab.device_table(flat.device)
+
+
+def neuron_scale(w0, w, tab, mask, delta=None, xi=None):
+    """w[row j] = (mask[j] + delta[j]) * w0[row j] for every row of every job of `tab`, and w[bias j] = (1 + xi[j]) * w0[bias j] where the job
+    has a bias (vd_neuron_scale: one launch for the whole table; delta / xi None: mask alone / the bias copied).  A raw-pointer write: whoever
+    scales network weights bumps WEIGHTS_EPOCH and calls the network's weights_changed() afterwards (as with `swap`)."""
+    table = _neuron_args(tab, w, mask, delta, xi)
+    assert w0.is_contiguous() and w0.dtype == torch.float32 and w0.numel() >= tab.extent and w0.data_ptr() != w.data_ptr()
+    nbytes = 8.0 * (tab.weight_floats + tab.n_bias) + 4.0 * tab.n_neurons * (1 + (delta is not None) + (xi is not None))
+    _timed("neuron_scale (neuron_scale_kernel)", nbytes, "hbm", lambda: L.check(           # w0 read, w written; one mask / delta / xi per row
+        _lib().vd_neuron_scale(_p(w0), _p(w), _p(table), tab.n_jobs, tab.total_blocks, _p(mask), _p(delta), _p(xi), _s()), "vd_neuron_scale"))
+    return w
+
+
+def neuron_grad(g, w0, tab, gmask, gxi=None, scale=1.0, accumulate=False):
+    """gmask[j] (+)= scale * <g[row j], w0[row j]> and gxi[j] (+)= scale * g[bias j] * w0[bias j] (vd_neuron_grad: one wave per row, fixed
+    order, bit-reproducible; a job without a bias leaves its gxi slots alone)."""
+    table = _neuron_args(tab, g, gmask, gxi)
+    assert w0.is_contiguous() and w0.dtype == torch.float32 and w0.numel() >= tab.extent
+    nbytes = 8.0 * (tab.weight_floats + tab.n_bias) + 4.0 * tab.n_neurons * (1 + bool(accumulate)) * (1 + (gxi is not None))
+    _timed("neuron_grad (neuron_grad_kernel)", nbytes, "hbm", lambda: L.check(             # g and w0 read; one gmask / gxi per row
+        _lib().vd_neuron_grad(_p(g), _p(w0), _p(table), tab.n_jobs, tab.total_blocks, _p(gmask), _p(gxi), float(scale), int(bool(accumulate)), _s()),
+        "vd_neuron_grad"))
+    return gmask
+
+
+def neuron_step(x, g, buf=None, *, lr, momentum=0.0, lo, hi, use_sign=False):
+    """x = clamp(x - lr * d, lo, hi) in place with d = buf <- momentum * buf + g (buf given), else sign(g) (use_sign) or g (vd_neuron_step, every
+    f32 operation rounded on its own; a negative lr ascends)."""
+    n = x.numel()
+    assert x.is_contiguous() and g.is_contiguous() and x.dtype == g.dtype == torch.float32 and g.numel() == n and float(lo) <= float(hi)
+    assert buf is None or (buf.is_contiguous() and buf.dtype == torch.float32 and buf.numel() == n)
+    _timed("neuron_step (neuron_step_kernel)", 4.0 * n * (5 if buf is not None else 3), "hbm", lambda: L.check(
+        _lib().vd_neuron_step(_p(x), _p(g), _p(buf), n, float(lr), float(momentum), float(lo), float(hi), int(bool(use_sign)), _s()),
+        "vd_neuron_step"))
+    return x
+
+
 def l2norm_sq(g, partial, out_sq):
     assert g.is_contiguous() and partial.numel() >= 1024
     _timed("l2norm_sq (sumsq_kernel)", 4.0 * g.numel(), "hbm",
