@@ -9,6 +9,10 @@ neuron-scaled weights, three mask-gradient reductions and the projected steps:
  * the two kernels alone over the full flat buffer, bytes over time against the 8 TB/s HBM peak: vd_neuron_scale (8 B/selected float) and
    vd_neuron_grad (8 B/selected float).
    python tools/anp_step_ab.py [--rounds 3] [--steps 20] [--out profiles/r11_anp_ab.json]
+--family ve / ldm measures the other two families' step instead (villandiffusion_amd.anp_ve on the default NCSN++, 32x32 at batch 64;
+villandiffusion_amd.anp_ldm's loss on config #5's latent UNet, 3x64x64 latents at batch 8): the mask-learning step ("kernels") alternating with
+its three forward + backward passes alone, without the neuron kernels ("passes"), and the two kernels over the whole flat buffer; the record
+goes under the family's name into profiles/r12_anp_families.json, beside whatever that file already holds.  Information only: no gate.
 Run it under a time limit of its own (`timeout -k 10 300 python tools/anp_step_ab.py`)."""
 import argparse
 import json
@@ -35,10 +39,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--out", default=os.path.join("profiles", "r11_anp_ab.json"))
+    ap.add_argument("--batch", type=int, default=None, help="default 64 (vp, ve), 8 (ldm)")
+    ap.add_argument("--family", choices=("vp", "ve", "ldm"), default="vp",
+                    help="vp: config #2's UNet against the per-layer torch leg (the default, as ever); ve / ldm: the family's step against its bare passes")
+    ap.add_argument("--out", default=None, help="default profiles/r11_anp_ab.json (vp), profiles/r12_anp_families.json (ve, ldm)")
     args = ap.parse_args()
     assert args.rounds >= 3
+    if args.batch is None:
+        args.batch = 8 if args.family == "ldm" else 64
+    if args.out is None:
+        args.out = os.path.join("profiles", "r11_anp_ab.json" if args.family == "vp" else "r12_anp_families.json")
 
     import torch
     from villandiffusion_amd import anp, ops
@@ -77,24 +87,51 @@ def main():
                     d = net.flat_grad[bo:bo + bn] * self.w0[bo:bo + bn] * scale
                     gxi[sl] = gxi[sl] + d if accumulate else d
 
+    class BarePasses(anp._Passes):
+        """The other families' leg B: the step's three forward + backward passes at the base weights, no neuron kernel."""
+
+        def write(self, mask, delta, xi):
+            pass
+
+        def step(self, st, x_t, y, t, start, cfg, curves):
+            for k in range(3):
+                self.run(x_t, y, t, st.mask, None, None, curves[k:k + 1])
+
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
-    net = UNet2DModel()
+    family, label, leg_b = None, "UNet2DModel CIFAR10 32x32", TorchPasses
+    if args.family == "ve":
+        from villandiffusion_amd import anp_ve
+        from villandiffusion_amd.ncsnpp import NCSNppModel
+        net, sched, label, leg_b = NCSNppModel(), S.ScoreSdeVeScheduler(), "NCSNppModel 32x32 (the default)", BarePasses
+    elif args.family == "ldm":
+        from villandiffusion_amd.loss import SDE_LDM, LossFn
+        from villandiffusion_amd.model import LDM_CELEBA_UNET_ARCH
+        net, sched = UNet2DModel(**{k: (tuple(v) if isinstance(v, list) else v) for k, v in LDM_CELEBA_UNET_ARCH.items()}), S.DDIMScheduler()
+        label, leg_b = "LDM-CELEBA-HQ-256 latent UNet, 3x64x64 latents", BarePasses
+    else:
+        net, sched = UNet2DModel(), S.DDPMScheduler()
     net.reset_parameters(0)
-    sched = S.DDPMScheduler()
+    if args.family == "ve":
+        family = anp_ve._family(net, sched)
+    elif args.family == "ldm":
+        family = anp._vp_family(sched, LossFn(sched, SDE_LDM, psi=1))
+    b_key = "torch_ms" if args.family == "vp" else "passes_ms"
     tab = anp.neuron_table(net, "all")
     n, B = tab.n_neurons, args.batch
+    Sz = int(net.sample_size)
     gen = torch.Generator().manual_seed(0)
-    x0 = (torch.rand(B, 3, 32, 32, generator=gen) * 2 - 1).to(dev)
-    eps = torch.randn(B, 3, 32, 32, generator=gen).to(dev)
-    t = torch.randint(0, 1000, (B,), generator=gen).to(dev)
+    x0 = torch.rand(B, 3, Sz, Sz, generator=gen)
+    x0 = (x0 if args.family == "ve" else x0 * 2 - 1).to(dev)           # the family's value range
+    eps = torch.randn(B, 3, Sz, Sz, generator=gen).to(dev)
+    t = torch.randint(0, int(sched.config.num_train_timesteps), (B,), generator=gen).to(dev)
     start = ((torch.rand(2, n, generator=gen) * 2 - 1) * 0.4).to(dev)
     cfg = SimpleNamespace(anp_eps=0.4, anp_steps=1, anp_alpha=0.2, lr=0.0, momentum=0.9)       # lr 0: every step of both legs sees the mask at 1
     curves = torch.zeros(3, device=dev)
     before = net.flat_param.clone()
-    rows = {"kernels_ms": [], "torch_ms": []}
-    with _trainable(net):
-        legs = {"kernels_ms": anp._Passes(net, sched, tab), "torch_ms": TorchPasses(net, sched, tab)}
+    rows = {"kernels_ms": [], b_key: []}
+    with _trainable(net, family.skip if family is not None else ()):
+        legs = {"kernels_ms": anp._Passes(net, sched, tab, family), b_key: leg_b(net, sched, tab, family)}
         states = {k: anp._state(n, dev) for k in legs}
         try:
             x_t, y = legs["kernels_ms"].inputs(x0, eps, t)
@@ -106,9 +143,10 @@ def main():
                     rows[key].append(timed(torch, fn, args.steps))
                 print(f"round {rnd}: " + ", ".join(f"{key[:-3]} {v[-1]:.3f} ms" for key, v in rows.items()), flush=True)
             # the two legs computed the same step: delta after the ascent, and the mask gradient up to the order of the row sums
-            a, b = states["kernels_ms"], states["torch_ms"]
-            same_delta = float((a.delta != b.delta).float().mean())
-            gm_rel = float((a.gm - b.gm).abs().max() / b.gm.abs().max())
+            a, b = states["kernels_ms"], states[b_key]
+            if args.family == "vp":
+                same_delta = float((a.delta != b.delta).float().mean())
+                gm_rel = float((a.gm - b.gm).abs().max() / b.gm.abs().max())
 
             # ---- the kernels alone ----
             ps = legs["kernels_ms"]
@@ -134,14 +172,20 @@ def main():
         print(f"{name}: {kk['us_median']:.1f} us, {kk['bytes'] / 1e6:.1f} MB, {kk['TB_per_s']:.3f} TB/s", flush=True)
     spread = lambda x: max(x) - min(x)
     summary = {key + "_median": med(x) for key, x in rows.items()} | {key + "_spread": spread(x) for key, x in rows.items()}
-    summary["kernels_over_torch"] = summary["kernels_ms_median"] / summary["torch_ms_median"]
-    summary["delta_mismatch_share"] = same_delta
-    summary["mask_gradient_max_rel_diff"] = gm_rel
-    out = {"config": {"model": "UNet2DModel CIFAR10 32x32", "parameters": net.flat_numel, "batch": B, "layers": "all", "neurons": n,
+    if args.family == "vp":
+        summary["kernels_over_torch"] = summary["kernels_ms_median"] / summary["torch_ms_median"]
+        summary["delta_mismatch_share"] = same_delta
+        summary["mask_gradient_max_rel_diff"] = gm_rel
+    else:
+        summary["kernels_over_passes"] = summary["kernels_ms_median"] / summary["passes_ms_median"]
+    out = {"config": {"model": label, "parameters": net.flat_numel, "batch": B, "layers": "all", "neurons": n,
                       "jobs": tab.n_jobs, "selected_floats": tab.weight_floats, "anp_steps": 1, "passes_per_step": 3, "rounds": args.rounds,
                       "steps": args.steps, "warmup": args.warmup, "conv_math": net.conv_math, "device": torch.cuda.get_device_name(0)},
            "rounds": rows, "kernels": kern, "summary": summary}
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    if args.family != "vp":                                # one file for both families: this run's record replaces its own, the other stays
+        held = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        out = held | {args.family: out}
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
     print(json.dumps(summary))

@@ -19,7 +19,10 @@ the host inside the loop.
 
 `prune_neurons` then zeroes the weight rows of the selected neurons (biases stay); the result is an ordinary diffusers-format checkpoint.
 
-Pixel-space VP-type `UNet2DModel`s, single process.  (NCSN++ / SDE-VE, latent diffusion and data-parallel mask learning are not built.)
+This module is the pixel-space VP-type `UNet2DModel`'s; `anp_ve` (NCSN++ with `ScoreSdeVeScheduler`) and `anp_ldm` (`LDMPipeline`) carry the same
+names.  The pass sequence, the state vectors, the argument checks, the restore discipline, `NeuronMask` and the three loops (`_run_objective`,
+`_run_learning`, `_run_curve`) live here once, parameterised by a `_Family`: a loss object, how the model is called (t or sigma_t, without or
+with a `pscale`) and the parameters that are never unfrozen.  Single process.  (Data-parallel mask learning is not built.)
 """
 from __future__ import annotations
 
@@ -34,7 +37,7 @@ from . import ops
 from .defense import _check_loop_args, _noise_of, _shape, _trainable
 from .mitigation import _check_f16
 
-__all__ = ["NeuronTable", "neuron_table", "anp_objective", "NeuronMask", "learn_neuron_mask", "prune_neurons"]
+__all__ = ["NeuronTable", "neuron_table", "anp_objective", "NeuronMask", "learn_neuron_mask", "prune_neurons"]     # (+ pruning_curve, by name)
 
 LAYERS = ("conv", "all")
 
@@ -46,10 +49,11 @@ def _check_model(what, model, noise_sched):
     if not isinstance(model, UNet2DModel):
         raise TypeError(f"{what} needs a villandiffusion_amd UNet2DModel, got {type(model).__name__}")
     if not getattr(model, "_input_grad", False):
-        raise NotImplementedError(f"{what}: {type(model).__name__} is out of scope (NCSN++ / score-SDE models are not built; VP-type UNet2DModel only)")
+        raise NotImplementedError(f"{what}: {type(model).__name__} is a score-SDE (VE) network; use villandiffusion_amd.anp_ve (anp is for the "
+                                  f"pixel-space VP-type UNet2DModel; an LDMPipeline goes to villandiffusion_amd.anp_ldm)")
     if isinstance(noise_sched, (ScoreSdeVeScheduler, KarrasVeScheduler)) or not hasattr(noise_sched, "alphas_cumprod"):
         raise NotImplementedError(f"{what}: {type(noise_sched).__name__} is a VE-type scheduler; the clean loss here is the VP-type (DDPM-style) "
-                                  f"noise-prediction loss")
+                                  f"noise-prediction loss (NCSNppModel with ScoreSdeVeScheduler goes to villandiffusion_amd.anp_ve)")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the neuron table
@@ -91,15 +95,21 @@ class NeuronTable:
         return self._dev[key]
 
 
+def _is_output_head(name: str) -> bool:
+    return name == "conv_out.weight" or (name.startswith("up_blocks.") and name.endswith(".skip_conv.weight"))
+
+
 def neuron_table(model, layers: str = "conv") -> NeuronTable:
     """The neurons of `model` (any flat-parameter network; pure host code, a device="cpu" model will do).  layers="conv": every parameter named
     *.weight with 4 dimensions; "all": every parameter with >= 2 dimensions (adds the attention projections and the time-embedding linears).
-    `conv_out.weight` is never selected: its rows are the image channels.  A neuron's bias is <prefix>.bias where the model has one."""
+    A weight whose rows are the network's output (image) channels is never selected: `conv_out.weight`, and the heads of NCSN++'s output-image
+    pyramid, `up_blocks.*.skip_conv.weight` (`down_blocks.*.skip_conv.weight`, whose rows are feature channels, is an ordinary layer).  A 1-d
+    parameter (NCSN++'s fixed `time_proj.weight`) is no layer.  A neuron's bias is <prefix>.bias where the model has one."""
     if layers not in LAYERS:
         raise ValueError(f"neuron_table: layers must be one of {LAYERS}, got {layers!r}")
     jobs, slices, neuron, block = [], {}, 0, 0
     for name, shape, _ in model._layout:
-        if name == "conv_out.weight" or not (len(shape) >= 2 if layers == "all" else (len(shape) == 4 and name.endswith(".weight"))):
+        if _is_output_head(name) or not (len(shape) >= 2 if layers == "all" else (len(shape) == 4 and name.endswith(".weight"))):
             continue
         off, n, _ = model._offs[name]
         rows = int(shape[0])
@@ -115,25 +125,55 @@ def neuron_table(model, layers: str = "conv") -> NeuronTable:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ one evaluation
+@dataclass(frozen=True)
+class _Family:
+    """What a model family brings to the shared passes.  loss: an object with `get_inputs_targets(x0, R, t, eps)` (a `LossFn`); call: t (int64
+    timestep indices on the device) -> (what the model is called with, the `pscale` of the loss kernel or None); skip: parameters that are
+    never unfrozen; T_train: how many timesteps the loss tables hold.  clean_shape / prepare: a family whose clean set may arrive in another
+    space (latent diffusion's pixel images) names that set's (C, H, W) and the map onto the model's input, which runs once, on the device, after
+    every check; None: the clean set is the model's input."""
+    loss: object
+    call: Callable
+    skip: tuple
+    T_train: int
+    clean_shape: Optional[tuple] = None
+    prepare: Optional[Callable] = None
+
+
 def _loss_fn(noise_sched):
     from .loss import SDE_VP, LossFn
     return LossFn(noise_sched, SDE_VP, psi=1)
 
 
-class _Passes:
-    """The state the passes of one call share: the base weights `w0` (a clone), the table, the loss tables and the scratch of the loss kernel."""
+def _vp_family(noise_sched, loss=None, clean_shape=None, prepare=None) -> _Family:
+    """The VP-type family: the model is called with the timestep itself and predicts the noise."""
+    return _Family(loss=loss if loss is not None else _loss_fn(noise_sched), call=lambda t: (t, None), skip=(),
+                   T_train=int(noise_sched.config.num_train_timesteps), clean_shape=clean_shape, prepare=prepare)
 
-    def __init__(self, model, noise_sched, tab: NeuronTable):
-        self.model, self.tab, self.lf = model, tab, _loss_fn(noise_sched)
+
+class _Passes:
+    """The state the passes of one call share: the base weights `w0` (a clone), the table, the loss tables and the scratch of the loss kernel.
+    family: a `_Family` (default: the VP-type one of `noise_sched`)."""
+
+    def __init__(self, model, noise_sched, tab: NeuronTable, family: Optional[_Family] = None):
+        self.fam = family if family is not None else _vp_family(noise_sched)
+        self.model, self.tab, self.lf = model, tab, self.fam.loss
         self.w0 = model.flat_param.detach().clone()
         self.partial = torch.empty(1024, device=model.device, dtype=torch.float32)
         self.zero_R = None
+        self._called = (None, None, None)
 
     def inputs(self, x0, eps, t):
-        """(x_t, y): q_sample of clean images and the target of the clean loss (the noise: the poison image is zero)."""
+        """(x_t, y): the noised clean images and the target of the clean loss (the noise: the poison image is zero)."""
         if self.zero_R is None or self.zero_R.shape != x0.shape:
             self.zero_R = torch.zeros_like(x0)
         return self.lf.get_inputs_targets(x0, self.zero_R, t, eps)
+
+    def call_args(self, t):
+        """(what the model is called with, pscale) at the timesteps t; worked out once per batch, not once per pass."""
+        if self._called[0] is not t:
+            self._called = (t,) + tuple(self.fam.call(t))
+        return self._called[1:]
 
     def write(self, mask, delta, xi):
         """flat_param <- the neuron-scaled base weights.  A raw-pointer write: no version counter sees it, so the caches derived from the weights
@@ -145,15 +185,24 @@ class _Passes:
     def run(self, x_t, y, t, mask, delta, xi, loss):
         """Forward + backward at (mask + delta, 1 + xi): `loss` ([1] view) is written, model.flat_grad holds the weight gradients of this pass."""
         model = self.model
+        tm, pscale = self.call_args(t)
         self.write(mask, delta, xi)
         model.zero_grad()
         with torch.enable_grad():
-            pred = model(x_t, t)[0]
+            pred = model(x_t, tm)[0]
         if pred.grad_fn is None:
             raise RuntimeError("adversarial neuron pruning: the model did not take its training forward (are all of its parameters frozen?)")
         dpred = torch.empty_like(pred)
-        ops.mse_fwd_bwd(pred.detach().contiguous(), y, dpred, loss, self.partial)
+        ops.mse_fwd_bwd(pred.detach().contiguous(), y, dpred, loss, self.partial, pscale=pscale)
         pred.backward(dpred)
+
+    def forward_loss(self, x_t, y, t, mask, loss):
+        """The no-grad forward at the weights mask * w0 (biases as they are): `loss` ([1] view) is written.  No gradient is touched."""
+        tm, pscale = self.call_args(t)
+        self.write(mask, None, None)
+        with torch.no_grad():
+            pred = self.model(x_t, tm)[0]
+        ops.mse_fwd_bwd(pred.contiguous(), y, torch.empty_like(pred), loss, self.partial, pscale=pscale)
 
     def grad(self, gmask, gxi, scale=1.0, accumulate=False):
         """gmask (+)= scale * dL/dmask, gxi (+)= scale * dL/dxi of the pass that has just run."""
@@ -203,20 +252,12 @@ def _check_per_neuron(what, name, v, n):
         raise ValueError(f"{what}: {name} must be a [{n}] tensor (one entry per neuron), got {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}")
 
 
-def anp_objective(model, noise_sched, clean: torch.Tensor, t: torch.Tensor, eps: torch.Tensor, mask: torch.Tensor,
-                  delta: Optional[torch.Tensor] = None, xi: Optional[torch.Tensor] = None, layers: Optional[str] = None):
-    """(loss, gmask, gxi) device tensors of the clean loss mse(model(q_sample(clean, eps, t), t), eps) at the weights (mask + delta) * w rows and
-    (1 + xi) * b biases: loss [1], gmask = dL/dmask = dL/ddelta [n], gxi = dL/dxi [n] (zero where a neuron has no bias).  mask (delta, xi): one
-    entry per neuron in `neuron_table` order; layers=None takes the selection whose neuron count mask has.  `flat_param` is restored bit for bit and
-    the requires_grad flags come back on exit.  For tests and for callers with an optimiser of their own."""
-    what = "anp_objective"
-    _check_model(what, model, noise_sched)
-    _check_f16(what, model)
-    shape = _shape(model)
-    _check_clean(what, clean, shape)
-    if not torch.is_tensor(eps) or tuple(eps.shape) != tuple(clean.shape):
-        raise ValueError(f"{what}: eps must be like clean {tuple(clean.shape)}, got {tuple(eps.shape) if torch.is_tensor(eps) else type(eps).__name__}")
+def _check_objective_args(what, model, clean, t, eps, mask, delta, xi, layers, clean_shape=None):
+    """-> the neuron table.  Everything about one evaluation that can be checked without the device."""
+    _check_clean(what, clean, clean_shape or _shape(model))
     B = clean.shape[0]
+    if not torch.is_tensor(eps) or tuple(eps.shape) != (B,) + _shape(model):
+        raise ValueError(f"{what}: eps must be like clean {(B,) + _shape(model)}, got {tuple(eps.shape) if torch.is_tensor(eps) else type(eps).__name__}")
     if not torch.is_tensor(t) or t.numel() != B:
         raise ValueError(f"{what}: t must hold one timestep per image ({B})")
     if not torch.is_tensor(mask) or mask.dim() != 1:
@@ -228,16 +269,24 @@ def anp_objective(model, noise_sched, clean: torch.Tensor, t: torch.Tensor, eps:
     for name, v in (("delta", delta), ("xi", xi)):
         if v is not None:
             _check_per_neuron(what, name, v, tab.n_neurons)
+    return tab
+
+
+def _run_objective(what, model, tab, family, clean, t, eps, mask, delta, xi):
+    """One evaluation for any family, after the caller's checks: (loss [1], gmask [n], gxi [n]) on the device.  `flat_param` is restored bit for
+    bit and the requires_grad flags come back on exit."""
     from . import lib
     lib.require_device()
     dev = model.device
     up = lambda v: None if v is None else v.detach().to(dev, torch.float32).contiguous()
     mask, delta, xi = up(mask), up(delta), up(xi)
+    if family.prepare is not None:
+        clean = family.prepare(clean, int(clean.shape[0]))
     loss = torch.empty(1, device=dev, dtype=torch.float32)
     gmask = torch.empty(tab.n_neurons, device=dev, dtype=torch.float32)
     gxi = torch.zeros(tab.n_neurons, device=dev, dtype=torch.float32)
-    with _trainable(model):
-        ps = _Passes(model, noise_sched, tab)
+    with _trainable(model, family.skip):
+        ps = _Passes(model, None, tab, family)
         try:
             tt = t.to(dev).reshape(-1).to(torch.int64)
             x_t, y = ps.inputs(up(clean), up(eps), tt)
@@ -246,6 +295,19 @@ def anp_objective(model, noise_sched, clean: torch.Tensor, t: torch.Tensor, eps:
         finally:
             ps.restore()
     return loss, gmask, gxi
+
+
+def anp_objective(model, noise_sched, clean: torch.Tensor, t: torch.Tensor, eps: torch.Tensor, mask: torch.Tensor,
+                  delta: Optional[torch.Tensor] = None, xi: Optional[torch.Tensor] = None, layers: Optional[str] = None):
+    """(loss, gmask, gxi) device tensors of the clean loss mse(model(q_sample(clean, eps, t), t), eps) at the weights (mask + delta) * w rows and
+    (1 + xi) * b biases: loss [1], gmask = dL/dmask = dL/ddelta [n], gxi = dL/dxi [n] (zero where a neuron has no bias).  mask (delta, xi): one
+    entry per neuron in `neuron_table` order; layers=None takes the selection whose neuron count mask has.  `flat_param` is restored bit for bit and
+    the requires_grad flags come back on exit.  For tests and for callers with an optimiser of their own."""
+    what = "anp_objective"
+    _check_model(what, model, noise_sched)
+    _check_f16(what, model)
+    tab = _check_objective_args(what, model, clean, t, eps, mask, delta, xi, layers)
+    return _run_objective(what, model, tab, _vp_family(noise_sched), clean, t, eps, mask, delta, xi)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ learning the mask
@@ -317,33 +379,20 @@ def _of_step(what, name, src, it, shape, dev, dtype):
     return v.detach().to(dev, dtype).contiguous()
 
 
-def learn_neuron_mask(model, noise_sched, clean: torch.Tensor, *, steps: int, batch: int, anp_eps: float = 0.4, anp_steps: int = 1,
-                      anp_alpha: float = 0.2, lr: float = 0.2, momentum: float = 0.9, layers: str = "conv", seed: int = 0,
-                      timesteps: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None,
-                      noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None,
-                      perturbation: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None) -> NeuronMask:
-    """Learn ANP's neuron mask on the clean images `clean` ([N, C, H, W] f32 in the model's value range; used in order and cyclically, `batch`
-    per step).  The model is left exactly as it was found.  One step, with the same images, timesteps and noise in every pass:
-
-      1. anp_eps > 0: delta, xi <- U(-anp_eps, anp_eps); anp_steps times: pass at (m + delta, 1 + xi), then
-         delta, xi <- clamp(. + (anp_eps / anp_steps) * sign(gradient), +-anp_eps);
-      2. anp_eps > 0: the robust pass at (m + delta, 1 + xi):  gm  = (1 - anp_alpha) * dL/dm;
-      3. the natural pass at (m, 1):                           gm += anp_alpha * dL/dm     (anp_eps == 0: the only pass, weight 1);
-      4. buf <- momentum * buf + gm;  m <- clamp(m - lr * buf, 0, 1).
-
-    The mask starts at 1.  The uniform draws are (torch.rand((steps, 2, n), generator=CPU Generator(seed)) * 2 - 1) * anp_eps, drawn up front
-    -- row [step, 0] is delta's start, [step, 1] xi's -- unless `perturbation` supplies them (that tensor, or a callable step -> [2, n]).
-    timesteps: None -- torch.randint(0, T, (steps, batch)) from a CPU Generator(seed + 1), drawn up front; a [steps, batch] tensor or a callable
-    step -> [batch].  noise: None -- fresh per step from the device Philox stream of `seed`; a [steps, batch, C, H, W] tensor or a callable
-    step -> [batch, C, H, W].  Tensors and callables make a run reproducible against another implementation."""
-    what = "learn_neuron_mask"
+def _run_learning(what, model, family, clean, steps, batch, anp_eps, anp_steps, anp_alpha, lr, momentum, layers, seed, timesteps, noise,
+                  perturbation) -> NeuronMask:
+    """The mask-learning loop of `learn_neuron_mask` (its docstring) for any family: the argument checks that need no device, the draws, the
+    loop, the restore.  The caller has checked that `model` (and its arithmetic) belongs to `family`."""
     anp_eps, anp_alpha, lr, momentum = float(anp_eps), float(anp_alpha), float(lr), float(momentum)
-    _check_model(what, model, noise_sched)
-    _check_f16(what, model)
     shape = _shape(model)
-    T_train = int(noise_sched.config.num_train_timesteps)
-    tab = _check_learn_args(what, model, clean, steps, batch, anp_eps, anp_steps, anp_alpha, lr, momentum, layers, timesteps, noise, perturbation,
-                            shape, T_train)
+    T_train = family.T_train
+    if family.clean_shape is not None:                     # the clean set arrives in another space: its own shape check, then a stand-in
+        _check_clean(what, clean, family.clean_shape)
+        stand_in = torch.empty((clean.shape[0],) + shape, device="meta", dtype=torch.float32)
+    else:
+        stand_in = clean
+    tab = _check_learn_args(what, model, stand_in, steps, batch, anp_eps, anp_steps, anp_alpha, lr, momentum, layers, timesteps, noise,
+                            perturbation, shape, T_train)
     n = tab.n_neurons
     adversarial = anp_eps > 0.0
     if adversarial and perturbation is None:
@@ -354,6 +403,8 @@ def learn_neuron_mask(model, noise_sched, clean: torch.Tensor, *, steps: int, ba
     from . import lib
     lib.require_device()                                   # VillanHipError without an MI355X: there is no fallback
     dev = model.device
+    if family.prepare is not None:
+        clean = family.prepare(clean, batch)
     data = clean.detach().to(dev, torch.float32).contiguous()
     N = data.shape[0]
     if torch.is_tensor(timesteps):
@@ -366,8 +417,8 @@ def learn_neuron_mask(model, noise_sched, clean: torch.Tensor, *, steps: int, ba
     eps_buf = torch.empty((batch,) + shape, device=dev, dtype=torch.float32)
     x0_buf = torch.empty_like(eps_buf)
     per_iter = (eps_buf.numel() + 3) // 4                  # Philox counters one step's noise consumes (four normals each)
-    with _trainable(model):                                # every weight gradient is needed; the caller's flags come back on exit
-        ps = _Passes(model, noise_sched, tab)
+    with _trainable(model, family.skip):                   # every weight gradient is needed; the caller's flags come back on exit
+        ps = _Passes(model, None, tab, family)
         try:
             for it in range(steps):
                 first = (it * batch) % N
@@ -393,46 +444,83 @@ def learn_neuron_mask(model, noise_sched, clean: torch.Tensor, *, steps: int, ba
     return res
 
 
+def learn_neuron_mask(model, noise_sched, clean: torch.Tensor, *, steps: int, batch: int, anp_eps: float = 0.4, anp_steps: int = 1,
+                      anp_alpha: float = 0.2, lr: float = 0.2, momentum: float = 0.9, layers: str = "conv", seed: int = 0,
+                      timesteps: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None,
+                      noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None,
+                      perturbation: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None) -> NeuronMask:
+    """Learn ANP's neuron mask on the clean images `clean` ([N, C, H, W] f32 in the model's value range; used in order and cyclically, `batch`
+    per step).  The model is left exactly as it was found.  One step, with the same images, timesteps and noise in every pass:
+
+      1. anp_eps > 0: delta, xi <- U(-anp_eps, anp_eps); anp_steps times: pass at (m + delta, 1 + xi), then
+         delta, xi <- clamp(. + (anp_eps / anp_steps) * sign(gradient), +-anp_eps);
+      2. anp_eps > 0: the robust pass at (m + delta, 1 + xi):  gm  = (1 - anp_alpha) * dL/dm;
+      3. the natural pass at (m, 1):                           gm += anp_alpha * dL/dm     (anp_eps == 0: the only pass, weight 1);
+      4. buf <- momentum * buf + gm;  m <- clamp(m - lr * buf, 0, 1).
+
+    The mask starts at 1.  The uniform draws are (torch.rand((steps, 2, n), generator=CPU Generator(seed)) * 2 - 1) * anp_eps, drawn up front
+    -- row [step, 0] is delta's start, [step, 1] xi's -- unless `perturbation` supplies them (that tensor, or a callable step -> [2, n]).
+    timesteps: None -- torch.randint(0, T, (steps, batch)) from a CPU Generator(seed + 1), drawn up front; a [steps, batch] tensor or a callable
+    step -> [batch].  noise: None -- fresh per step from the device Philox stream of `seed`; a [steps, batch, C, H, W] tensor or a callable
+    step -> [batch, C, H, W].  Tensors and callables make a run reproducible against another implementation."""
+    what = "learn_neuron_mask"
+    _check_model(what, model, noise_sched)
+    _check_f16(what, model)
+    return _run_learning(what, model, _vp_family(noise_sched), clean, steps, batch, anp_eps, anp_steps, anp_alpha, lr, momentum, layers, seed,
+                         timesteps, noise, perturbation)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------- pruning
-def prune_neurons(model, mask, *, threshold: Optional[float] = None, fraction: Optional[float] = None) -> Dict[str, int]:
-    """Zero the weight rows of the neurons `mask` (a NeuronMask, or a weight name -> [rows] dict) selects, in place: threshold prunes m_j <
-    threshold (ANP's default is 0.2); fraction prunes the floor(fraction * n) smallest masks of the whole network, ties by neuron index.  Biases
-    stay and every other float keeps its bits.  A selection that would prune a whole layer raises ValueError naming it before anything is
-    written.  Plain torch writes: works on a device="cpu" model.  -> weight name -> rows pruned."""
+def _selection(who, model, mask, threshold=None, fraction=None):
+    """-> (the "all" neuron table, drop: a bool per neuron of that table, picks: weight name -> the row indices to zero, for the layers `mask`
+    names).  The selection rule of `prune_neurons` (its docstring), with every check of it; pure host code, nothing is written."""
     if (threshold is None) == (fraction is None):
-        raise ValueError("prune_neurons: give exactly one of threshold and fraction")
+        raise ValueError(f"{who}: give exactly one of threshold and fraction")
     masks = mask.masks if isinstance(mask, NeuronMask) else mask
     if not isinstance(masks, dict) or not masks:
-        raise TypeError(f"prune_neurons: mask must be a NeuronMask or a non-empty dict name -> [rows] tensor, got {type(mask).__name__}")
-    order = [name for name in neuron_table(model, "all").slices if name in masks]          # neuron-table order, whatever the dict's
+        raise TypeError(f"{who}: mask must be a NeuronMask or a non-empty dict name -> [rows] tensor, got {type(mask).__name__}")
+    full = neuron_table(model, "all")
+    order = [name for name in full.slices if name in masks]          # neuron-table order, whatever the dict's
     unknown = [name for name in masks if name not in order]
     if unknown:
-        raise ValueError(f"prune_neurons: {unknown[:3]} are not neuron layers of this {type(model).__name__}")
+        raise ValueError(f"{who}: {unknown[:3]} are not neuron layers of this {type(model).__name__}")
     for name in order:
         rows = int(model._offs[name][2][0])
         if not torch.is_tensor(masks[name]) or masks[name].numel() != rows:
-            raise ValueError(f"prune_neurons: the mask of {name} must hold {rows} entries")
+            raise ValueError(f"{who}: the mask of {name} must hold {rows} entries")
     flat = torch.cat([masks[name].detach().reshape(-1).to("cpu", torch.float32) for name in order])
     n = flat.numel()
     if threshold is not None:
         threshold = float(threshold)
         if not math.isfinite(threshold):
-            raise ValueError(f"prune_neurons: threshold must be finite, got {threshold!r}")
+            raise ValueError(f"{who}: threshold must be finite, got {threshold!r}")
         drop = flat < threshold
     else:
         fraction = float(fraction)
         if not 0.0 <= fraction < 1.0:
-            raise ValueError(f"prune_neurons: fraction must lie in [0, 1), got {fraction!r}")
+            raise ValueError(f"{who}: fraction must lie in [0, 1), got {fraction!r}")
         drop = torch.zeros(n, dtype=torch.bool)
         drop[torch.sort(flat, stable=True).indices[:int(math.floor(fraction * n))]] = True      # stable: ties by neuron index
     picks, first = {}, 0
+    dropped = torch.zeros(full.n_neurons, dtype=torch.bool)
     for name in order:
         rows = masks[name].numel()
         idx = drop[first:first + rows].nonzero().reshape(-1)
         if idx.numel() == rows:
-            raise ValueError(f"prune_neurons: the selection prunes every neuron of {name}; nothing was written")
+            raise ValueError(f"{who}: the selection prunes every neuron of {name}; nothing was written")
         picks[name] = idx
+        dropped[full.slices[name]] = drop[first:first + rows]
         first += rows
+    return full, dropped, picks
+
+
+def prune_neurons(model, mask, *, threshold: Optional[float] = None, fraction: Optional[float] = None) -> Dict[str, int]:
+    """Zero the weight rows of the neurons `mask` (a NeuronMask, or a weight name -> [rows] dict) selects, in place: threshold prunes m_j <
+    threshold (ANP's default is 0.2); fraction prunes the floor(fraction * n) smallest masks of the whole network, ties by neuron index.  Biases
+    stay and every other float keeps its bits.  A selection that would prune a whole layer raises ValueError naming it before anything is
+    written; so does a mask that names a weight that is no neuron layer (`conv_out.weight`, NCSN++'s `up_blocks.*.skip_conv.weight`).  Plain
+    torch writes: works on a device="cpu" model, a `UNet2DModel` or an `NCSNppModel`.  -> weight name -> rows pruned."""
+    _, _, picks = _selection("prune_neurons", model, mask, threshold=threshold, fraction=fraction)
     with torch.no_grad():
         for name, idx in picks.items():
             if idx.numel():
@@ -440,3 +528,75 @@ def prune_neurons(model, mask, *, threshold: Optional[float] = None, fraction: O
     ops.WEIGHTS_EPOCH += 1                                  # writes through .data views: no version counter of flat_param sees them
     model.weights_changed()
     return {name: int(idx.numel()) for name, idx in picks.items()}
+
+
+# ------------------------------------------------------------------------------------------------------------------------- the pruning curve
+def _run_curve(what, model, family, clean, mask, thresholds, fractions, seed, timesteps, noise) -> List[dict]:
+    """`pruning_curve` (its docstring) for any family, after the caller's checks of the model."""
+    if (thresholds is None) == (fractions is None):
+        raise ValueError(f"{what}: give exactly one of thresholds and fractions")
+    key, cands = ("threshold", thresholds) if thresholds is not None else ("fraction", fractions)
+    try:
+        cands = [float(c) for c in cands]
+    except TypeError:
+        raise TypeError(f"{what}: {key}s must be a sequence of numbers, got {type(cands).__name__}") from None
+    shape = _shape(model)
+    _check_clean(what, clean, family.clean_shape or shape)
+    B = int(clean.shape[0])
+    if int(model.out_channels) != shape[0]:
+        raise ValueError(f"{what}: the loss compares the model's output with its input: out_channels {model.out_channels} != in_channels "
+                         f"{model.in_channels}")
+    if timesteps is not None:
+        if not torch.is_tensor(timesteps) or tuple(timesteps.shape) != (B,) or timesteps.is_floating_point():
+            raise ValueError(f"{what}: timesteps must be None or an integer [{B}] tensor, one per image")
+        if int(timesteps.min()) < 0 or int(timesteps.max()) >= family.T_train:
+            raise ValueError(f"{what}: timesteps outside the scheduler's [0, {family.T_train})")
+    if noise is not None and (not torch.is_tensor(noise) or tuple(noise.shape) != (B,) + shape):
+        raise ValueError(f"{what}: noise must be None or a {(B,) + shape} tensor, one unit-variance image per clean image")
+    sels = [_selection(what, model, mask, **{key: c}) for c in cands]             # ValueError for an emptied layer, before anything runs
+    tab = sels[0][0] if sels else neuron_table(model, "all")
+    hard = torch.ones((len(sels) + 1, tab.n_neurons), dtype=torch.float32)        # row 0: the unpruned model
+    for k, (_, dropped, _) in enumerate(sels):
+        hard[k + 1][dropped] = 0.0
+    if timesteps is None:
+        timesteps = torch.randint(0, family.T_train, (1, B), generator=torch.Generator().manual_seed(int(seed) + 1))[0]
+
+    from . import lib
+    lib.require_device()                                   # VillanHipError without an MI355X: there is no fallback
+    dev = model.device
+    hard = hard.to(dev)
+    if family.prepare is not None:
+        clean = family.prepare(clean, B)
+    x0 = clean.detach().to(dev, torch.float32).contiguous()
+    t = timesteps.to(dev, torch.int64).contiguous()
+    eps_buf = torch.empty_like(x0)
+    eps = _noise_of(what, None if noise is None else noise.unsqueeze(0), 0, eps_buf, seed, (eps_buf.numel() + 3) // 4, dev)
+    losses = torch.zeros(len(sels) + 1, device=dev, dtype=torch.float32)
+    ps = _Passes(model, None, tab, family)
+    try:
+        x_t, y = ps.inputs(x0, eps, t)
+        for k in range(len(sels) + 1):
+            ps.forward_loss(x_t, y, t, hard[k], losses[k:k + 1])
+    finally:
+        ps.restore()
+    host = losses.cpu().tolist()                           # the one read of the results
+    return [{key: None, "pruned": 0, "loss": float(host[0])}] + \
+        [{key: c, "pruned": int(sel[1].sum()), "loss": float(v)} for c, sel, v in zip(cands, sels, host[1:])]
+
+
+def pruning_curve(model, noise_sched, clean: torch.Tensor, mask, *, thresholds=None, fractions=None, seed: int = 0,
+                  timesteps: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None) -> List[dict]:
+    """The clean loss a learnt mask costs at each candidate selection: what an ANP user chooses the threshold with.  mask: a NeuronMask or a
+    name -> [rows] dict; thresholds= or fractions=: the candidates, each read as `prune_neurons` reads it.  -> one record per candidate,
+    {"threshold" | "fraction": the candidate, "pruned": rows it zeroes, "loss": the clean loss of the model with exactly those rows zeroed},
+    after record 0, the unpruned model (candidate None, pruned 0).
+
+    `clean` ([B, C, H, W]) is ONE batch; every record is a no-grad forward over the same images, timesteps and noise, at weights written by
+    `vd_neuron_scale` with a mask of zeros and ones and no xi (so biases, and the rows that stay, keep their bits).  timesteps: None --
+    torch.randint(0, T, (1, B)) from a CPU Generator(seed + 1), step 0's draw of the learning loop at batch B; or an integer [B] tensor.
+    noise: None -- the learning loop's step-0 draw from the device Philox stream of `seed`; or a tensor like clean.  A candidate that would
+    empty a layer raises ValueError naming it before anything runs.  The model is restored bit for bit, also after an exception."""
+    what = "pruning_curve"
+    _check_model(what, model, noise_sched)
+    _check_f16(what, model)
+    return _run_curve(what, model, _vp_family(noise_sched), clean, mask, thresholds, fractions, seed, timesteps, noise)
