@@ -40,14 +40,15 @@ MODE_SAMPLING_OPTS = {"project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt
                       "infer_start", "inpaint_mul", "task"}
 MODE_MEASURE_OPTS = MODE_SAMPLING_OPTS
 IGNORE_ARGS = {"overwrite", "is_save_all_model_epochs", "R_trigger_only"}
-# options of this build beyond the reference's: --ema_decay (train modes; resume takes it from args.json), --use_ema (sampling / measure).
+# options of this build beyond the reference's: --ema_decay (train modes; resume takes it from args.json), --use_ema (sampling / measure),
+# --lora_r / --lora_alpha / --lora_target (train modes: a LoRA fine-tune, villandiffusion_amd.lora; resume takes them from args.json).
 # At their defaults they are left out of the JSON side files, which then read as they did before the options existed.
 EXTRA_MODE_OPTS = {MODE_SAMPLING: {"use_ema"}, MODE_MEASURE: {"use_ema"}}
-EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False}
+EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False, "lora_r": None, "lora_alpha": None, "lora_target": "attn"}
 
 
 def _side_file(d: dict) -> dict:
-    return {k: v for k, v in d.items() if k != "extra" and not (k in EXTRA_DEFAULTS and v == EXTRA_DEFAULTS[k])}
+    return {k: v for k, v in d.items() if k != "extra" and not (k in EXTRA_DEFAULTS and (v is None or v == EXTRA_DEFAULTS[k]))}
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -79,6 +80,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     a("--is_save_all_model_epochs", "-isame", action="store_true"); a("--sample_ep", "-se", type=int); a("--result", "-res", type=str)
     # not in the reference: keep an exponential moving average of the weights while training (diffusers EMAModel; absent = off) / sample from it
     a("--ema_decay", type=float); a("--use_ema", action="store_true")
+    # not in this form in the reference (its --use_lora / --lora_r serve Stable Diffusion only): train a rank-r LoRA adapter instead of the weights
+    a("--lora_r", type=int); a("--lora_alpha", type=float); a("--lora_target", type=str, choices=["attn", "conv", "all"])
     return p.parse_args(argv)
 
 
@@ -100,6 +103,7 @@ class TrainingConfig:
     ckpt_dir: str = "ckpt"; data_ckpt_dir: str = "data.ckpt"; ep_model_dir: str = "epochs"
     clip: bool = False; output_dir: str = ""; ckpt_path: Optional[str] = None; data_ckpt_path: Optional[str] = None
     ema_decay: Optional[float] = None; use_ema: bool = False
+    lora_r: Optional[int] = None; lora_alpha: Optional[float] = None; lora_target: str = "attn"
     extra: dict = field(default_factory=dict)
 
 
@@ -138,6 +142,7 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
                 raise NotImplementedError(f"Argument: {k}={v} isn't supported in mode: {mode}")
             setattr(cfg, k, v)
     cfg.mode = mode
+    lora_config(cfg)                                                   # ValueError / NotImplementedError before anything is created
     cfg.clip = cfg.fclip == "w"                                        # :252-258
     # f32 tensors everywhere by default (reference :260-264: fp16 autocast + GradScaler for SDE-VP / SDE-LDM).  VILLAN_MIXED_PRECISION=fp16 opts
     # into the library's mixed-precision arithmetic (UNet2DModel.conv_math = "f16": single f16 products in the full-size convolutions, loss scaling);
@@ -187,6 +192,22 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
     if rank0:
         os.makedirs(cfg.ckpt_path, exist_ok=True)                      # :312-315
     return cfg
+
+
+def lora_config(cfg: TrainingConfig):
+    """The LoRAConfig the flags ask for, or None.  Raises for what is not built: LoRA with EMA, LoRA on more than one GPU."""
+    if cfg.lora_r is None:
+        if cfg.lora_alpha is not None or cfg.lora_target != EXTRA_DEFAULTS["lora_target"]:
+            raise ValueError("--lora_alpha / --lora_target need --lora_r")
+        return None
+    from villandiffusion_amd.lora import LoRAConfig
+    lc = LoRAConfig(r=cfg.lora_r, alpha=cfg.lora_alpha, target=cfg.lora_target, seed=cfg.seed)      # ValueError for a rank outside [1, 32]
+    if cfg.ema_decay is not None:
+        raise ValueError("--lora_r together with --ema_decay is not built")
+    training = cfg.mode in (MODE_TRAIN, MODE_RESUME, MODE_TRAIN_MEASURE)
+    if training and (len(str(cfg.gpu).split(",")) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        raise NotImplementedError("--lora_r on more than one GPU is not built")
+    return lc
 
 
 # ----------------------------------------------------------------------------------------------------------------- run
@@ -434,9 +455,10 @@ def checkpoint(cfg, trainer, pipeline, epoch, step, dsl=None):
     torch.save(data, cfg.data_ckpt_path)
     opt = trainer.opt
     ema = (opt.ema, opt.ema_cfg, opt.ema_step) if opt.ema is not None else None        # EMA on: unet_ema/ beside unet/
-    pipeline.save_pretrained(cfg.output_dir, ema=ema)
+    lora = getattr(trainer, "adapter", None)                           # LoRA on: unet_lora/ beside unet/ (which holds the merged weights)
+    pipeline.save_pretrained(cfg.output_dir, ema=ema, lora=lora)
     if cfg.is_save_all_model_epochs:                                   # reference :1110-1114: a copy per checkpointed epoch
-        pipeline.save_pretrained(get_ep_model_path(cfg, cfg.output_dir, epoch), ema=ema)
+        pipeline.save_pretrained(get_ep_model_path(cfg, cfg.output_dir, epoch), ema=ema, lora=lora)
 
 
 def get_ep_model_path(cfg, dir: str, epoch: int) -> str:
@@ -472,7 +494,8 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
                      vp_scale=cfg.vp_scale, ve_scale=cfg.ve_scale)
     n_batch = (len(dsl) + cfg.batch * world - 1) // (cfg.batch * world)
     trainer = Trainer(model, loss_fn, lr=cfg.learning_rate, total_steps=n_batch * cfg.epoch, warmup_steps=cfg.lr_warmup_steps,
-                      grad_accum=cfg.gradient_accumulation_steps, ema=EMAConfig(decay=cfg.ema_decay) if cfg.ema_decay is not None else None)
+                      grad_accum=cfg.gradient_accumulation_steps, ema=EMAConfig(decay=cfg.ema_decay) if cfg.ema_decay is not None else None,
+                      lora=lora_config(cfg))
     start_epoch, step = 0, 0
     if cfg.mode == MODE_RESUME:
         trainer.load_state_dict(torch.load(os.path.join(cfg.ckpt_path, "trainer.pt"), map_location=model.device))
@@ -577,6 +600,8 @@ def apply_gpu_flag(args: argparse.Namespace, argv: Optional[List[str]]):
     os.environ["CUDA_VISIBLE_DEVICES"] = plan["visible"]              # the name the reference sets (:240); HIP honours both
     if plan["action"] == "single":
         return plan
+    if getattr(args, "lora_r", None) is not None:                      # before the ranks start
+        raise NotImplementedError("--lora_r on more than one GPU is not built")
     import socket
     import subprocess
     with socket.socket() as sk:

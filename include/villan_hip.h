@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step: additions only */
+#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step / vd_lora_merge / vd_lora_grad: additions only */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -444,6 +444,27 @@ int vd_neuron_grad(const float* g, const float* w0, const int64_t* table, int n_
  *   x = min(max(x - lr * d, lo), hi)                    (torch: (x - lr * d).clamp(lo, hi), lr an f32)
  * A negative lr ascends. */
 int vd_neuron_step(float* x, const float* g, float* buf, int64_t n, float lr, float momentum, float lo, float hi, int use_sign, void* stream);
+/* LoRA fine-tuning (lora.py).  Both take an ADAPTER TABLE: a device array of n_jobs x 7 int64, one job per adapted weight tensor of a flat
+ * parameter buffer, {weight offset in floats, rows M, row length L, offset of A in the adapter buffer, offset of B in the adapter buffer, first
+ * row workgroup, first column workgroup}.  The weight is viewed as [M, L]; the ADAPTER BUFFER `ab` is one flat f32 buffer that holds, per job,
+ * A [r, L] row-major and then B [M, r] row-major, every piece starting at a multiple of 4 floats (the padding is never read and never written);
+ * `gab` mirrors it.  A job owns ceil(M / 4) row workgroups (one 64-lane wave per row) and ceil(L / 256) column workgroups (256 columns each);
+ * both first-workgroup columns ascend from 0.  One rank 1 <= r <= 32 per launch.  Rows need not be 16-byte aligned: where L is a multiple of 4
+ * and the job starts 16-byte aligned in every buffer a row moves as f32x4, otherwise as scalars, with the same values and sums either way.
+ *
+ * vd_lora_merge: w[row j][k] = w0[row j][k] + s * sum_{q<r} B[j][q] * A[q][k] for every job, the sum over q in ascending order from 0, every
+ * operation rounded on its own (B = 0 gives w0 + 0).  Floats of w outside every job are not written.  w != w0.  total_blocks: the row
+ * workgroups of the table. */
+int vd_lora_merge(const float* w0, float* w, const int64_t* table, int n_jobs, int64_t total_blocks, const float* ab, int r, float s, void* stream);
+/* gab.B[j][q] (+)= s * sum_k g[row j][k] * A[q][k];  gab.A[q][k] (+)= s * sum_j B[j][q] * g[row j][k];  accumulate != 0 adds to what is
+ * there.  g: the ordinary weight gradient, laid out like w.  One launch: total_blocks = the row workgroups of the table plus its column
+ * workgroups; the row workgroups come first.  g is read twice, the padding of gab is never written, no atomics: bit-reproducible.  The sums:
+ *   B[j][q]: with element k of a row in item k / 4, a lane keeps one f32 partial over its items lane, lane + 64, ... in that order, the four
+ *            elements of an item in index order; the 64 lanes are added by a fixed xor tree; the sum is multiplied by s.
+ *   A[q][k]: wave w of the four adds rows j = w, w + 4, w + 8, ... in that order in one f32 chain; the chains are added as
+ *            ((c0 + c1) + c2) + c3; the sum is multiplied by s. */
+int vd_lora_grad(const float* g, const int64_t* table, int n_jobs, int64_t total_blocks, const float* ab, float* gab, int r, float s,
+                 int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K9 -- global grad-norm clip + Adam on flat buffers (VillanDiffusion.py:445,1165-1169).

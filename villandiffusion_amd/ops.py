@@ -1152,6 +1152,36 @@ def neuron_step(x, g, buf=None, *, lr, momentum=0.0, lo, hi, use_sign=False):
     return x
 
 
+def _lora_args(tab, flat, *adapter):
+    """tab: lora.AdapterTable, resident on flat's device.  Every offset of its jobs is checked against the buffers here, on the host: the kernels
+    trust the table."""
+    assert flat.is_contiguous() and flat.dtype == torch.float32 and flat.numel() >= tab.extent, (flat.numel(), tab.extent)
+    for v in adapter:
+        assert v.is_contiguous() and v.dtype == torch.float32 and v.numel() >= tab.numel and v.device == flat.device, "adapter buffer"
+    return tab.device_table(flat.device)
+
+
+def lora_merge(w0, w, tab, ab):
+    """w[layer] = w0[layer] + s * B A for every job of `tab` (vd_lora_merge: one launch for the whole table; rank and s are the table's).  A
+    raw-pointer write: whoever merges into network weights bumps WEIGHTS_EPOCH and calls the network's weights_changed() afterwards."""
+    table = _lora_args(tab, w, ab)
+    assert w0.is_contiguous() and w0.dtype == torch.float32 and w0.numel() >= tab.extent and w0.data_ptr() != w.data_ptr()
+    _timed("lora_merge (lora_merge_kernel)", 8.0 * tab.weight_floats, "hbm", lambda: L.check(            # w0 read, w written; A, B from cache
+        _lib().vd_lora_merge(_p(w0), _p(w), _p(table), tab.n_jobs, tab.row_blocks, _p(ab), tab.r, float(tab.s), _s()), "vd_lora_merge"))
+    return w
+
+
+def lora_grad(g, tab, ab, gab, accumulate=False):
+    """gab.B (+)= s * G A^T and gab.A (+)= s * B^T G for every job of `tab`, G the layer's slice of the flat weight gradient `g` (vd_lora_grad:
+    one launch, fixed order, bit-reproducible; the padding of gab is left alone)."""
+    table = _lora_args(tab, g, ab, gab)
+    assert ab.data_ptr() != gab.data_ptr()
+    _timed("lora_grad (lora_grad_kernel)", 8.0 * tab.weight_floats, "hbm", lambda: L.check(              # g read twice: rows -> B, columns -> A
+        _lib().vd_lora_grad(_p(g), _p(table), tab.n_jobs, tab.row_blocks + tab.col_blocks, _p(ab), _p(gab), tab.r, float(tab.s),
+                            int(bool(accumulate)), _s()), "vd_lora_grad"))
+    return gab
+
+
 def l2norm_sq(g, partial, out_sq):
     assert g.is_contiguous() and partial.numel() >= 1024
     _timed("l2norm_sq (sumsq_kernel)", 4.0 * g.numel(), "hbm",

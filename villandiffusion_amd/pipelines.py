@@ -296,9 +296,13 @@ class DiffusionPipeline:
         return chunk * 2 * n_steps * ((numel + 3) // 4)
 
     # ---- diffusers on-disk layout ----
-    def save_pretrained(self, save_directory: str, safe_serialization: bool = True, ema=None):
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = True, ema=None, lora=None):
         """ema: (flat shadow, trainer.EMAConfig, ema_step) -- additionally writes `unet_ema/` beside `unet/`: the same two files with the weights
-        taken from the shadow, its config.json extended by the EMA state under diffusers' EMAModel names.  Everything else is written as without."""
+        taken from the shadow, its config.json extended by the EMA state under diffusers' EMAModel names.  lora: a `lora.LoRAAdapter` of this
+        pipeline's network -- additionally writes `unet_lora/` (adapter_config.json + adapter_model.safetensors); `unet/` holds the merged
+        weights, as the network does.  Everything else is written as without."""
+        if lora is not None and getattr(lora, "model", None) is not self.unet:
+            raise ValueError("save_pretrained: lora must be the LoRAAdapter of this pipeline's unet")
         os.makedirs(os.path.join(save_directory, "unet"), exist_ok=True)
         os.makedirs(os.path.join(save_directory, "scheduler"), exist_ok=True)
         index = {"_class_name": self._class_name, "_diffusers_version": "0.16.1",
@@ -345,6 +349,8 @@ class DiffusionPipeline:
                 save_file(esd, os.path.join(save_directory, "unet_ema", "diffusion_pytorch_model.safetensors"))
             else:
                 torch.save(esd, os.path.join(save_directory, "unet_ema", "diffusion_pytorch_model.bin"))
+        if lora is not None:
+            lora.save(os.path.join(save_directory, "unet_lora"))
         with open(os.path.join(save_directory, "scheduler", "scheduler_config.json"), "w") as f:
             json.dump({k: v for k, v in self.scheduler.scheduler_config().items() if v is None or isinstance(v, (int, float, str, bool, list))},
                       f, indent=2)

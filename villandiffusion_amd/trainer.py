@@ -232,10 +232,25 @@ class GraphedMicroStep:
 class Trainer:
     def __init__(self, model, loss_fn, lr: float, total_steps: int, warmup_steps: int = 500, grad_accum: int = 1,
                  max_grad_norm: Optional[float] = 1.0, n_allreduce_buckets: int = 4, graph_micro_step: Optional[bool] = None,
-                 force_ddp_path: bool = False, ema: Optional[EMAConfig] = None):
+                 force_ddp_path: bool = False, ema: Optional[EMAConfig] = None, lora=None):
         self.model, self.loss_fn = model, loss_fn
         self.base_lr = lr
-        self.opt = FusedAdam(model, lr, max_grad_norm=max_grad_norm, ema=ema)
+        self.adapter = None
+        if lora is not None:
+            # LoRA fine-tune (lora.py): the weights are frozen in a clone, the optimiser owns the flat adapter buffer alone, and every optimiser
+            # step ends by writing the merged weights back into flat_param.  Every check comes before the first launch.
+            from .lora import LoRAAdam, LoRAAdapter, LoRAConfig
+            if not isinstance(lora, LoRAConfig):
+                raise TypeError(f"Trainer: lora must be a LoRAConfig, got {type(lora).__name__}")
+            if ema is not None:
+                raise ValueError("Trainer: lora together with ema is not built (the shadow would average merged weights the adapter cannot express)")
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise NotImplementedError("Trainer: lora in a process group of more than one rank is not built (the adapter gradient is formed "
+                                          "from the local flat_grad)")
+            self.adapter = LoRAAdapter(model, lora)
+            self.opt = LoRAAdam(self.adapter, lr, max_grad_norm=max_grad_norm)
+        else:
+            self.opt = FusedAdam(model, lr, max_grad_norm=max_grad_norm, ema=ema)
         self._ema_swapped = False
         self.lr_lambda: Callable[[int], float] = get_cosine_schedule_with_warmup_lambda(warmup_steps, total_steps)
         self.grad_accum = max(1, int(grad_accum))
@@ -405,10 +420,18 @@ class Trainer:
             raise RuntimeError("state_dict() inside ema_weights(): the network holds the EMA weights and the shadow the raw ones")
         if getattr(self.model, "device", torch.device("cpu")).type == "cuda":
             self.check_skipped(force=True, count_step=False)      # a checkpoint never records steps the kernel refused
-        return {"optimizer": self.opt.state_dict(), "micro": self.micro, "sched_step": self.sched_step,
-                "loss_scale": self.loss_scale, "since_growth": self._since_growth, "overflow_steps_seen": self.overflow_steps_seen}
+        sd = {"optimizer": self.opt.state_dict(), "micro": self.micro, "sched_step": self.sched_step,
+              "loss_scale": self.loss_scale, "since_growth": self._since_growth, "overflow_steps_seen": self.overflow_steps_seen}
+        if self.adapter is not None:
+            sd["lora"] = self.adapter.train_state()
+        return sd
 
     def load_state_dict(self, sd: Dict):
+        if ("lora" in sd) != (self.adapter is not None):
+            raise ValueError("load_state_dict: the state " + ("holds a" if "lora" in sd else "holds no") + " LoRA adapter but this trainer was "
+                             "built " + ("without" if "lora" in sd else "with") + " one (Trainer lora=...)")
+        if self.adapter is not None:
+            self.adapter.load_train_state(sd["lora"])
         self.opt.load_state_dict(sd["optimizer"])
         self.micro, self.sched_step = int(sd["micro"]), int(sd["sched_step"])
         self.loss_scale = float(sd.get("loss_scale", self.loss_scale))          # (absent from checkpoints written before round 5)
