@@ -41,10 +41,11 @@ MODE_SAMPLING_OPTS = {"project", "mode", "eval_max_batch", "gpu", "fclip", "ckpt
 MODE_MEASURE_OPTS = MODE_SAMPLING_OPTS
 IGNORE_ARGS = {"overwrite", "is_save_all_model_epochs", "R_trigger_only"}
 # options of this build beyond the reference's: --ema_decay (train modes; resume takes it from args.json), --use_ema (sampling / measure),
-# --lora_r / --lora_alpha / --lora_target (train modes: a LoRA fine-tune, villandiffusion_amd.lora; resume takes them from args.json).
+# --lora_r / --lora_alpha / --lora_target / --lora_backward (train modes: a LoRA fine-tune, villandiffusion_amd.lora; resume takes them from
+# args.json).
 # At their defaults they are left out of the JSON side files, which then read as they did before the options existed.
 EXTRA_MODE_OPTS = {MODE_SAMPLING: {"use_ema"}, MODE_MEASURE: {"use_ema"}}
-EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False, "lora_r": None, "lora_alpha": None, "lora_target": "attn"}
+EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False, "lora_r": None, "lora_alpha": None, "lora_target": "attn", "lora_backward": None}
 
 
 def _side_file(d: dict) -> dict:
@@ -82,6 +83,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     a("--ema_decay", type=float); a("--use_ema", action="store_true")
     # not in this form in the reference (its --use_lora / --lora_r serve Stable Diffusion only): train a rank-r LoRA adapter instead of the weights
     a("--lora_r", type=int); a("--lora_alpha", type=float); a("--lora_target", type=str, choices=["attn", "conv", "all"])
+    # "adapted": the backward forms only the gradients the adapter needs (absent = "full": every weight gradient, as a full fine-tune does)
+    a("--lora_backward", type=str, choices=["full", "adapted"])
     return p.parse_args(argv)
 
 
@@ -103,7 +106,7 @@ class TrainingConfig:
     ckpt_dir: str = "ckpt"; data_ckpt_dir: str = "data.ckpt"; ep_model_dir: str = "epochs"
     clip: bool = False; output_dir: str = ""; ckpt_path: Optional[str] = None; data_ckpt_path: Optional[str] = None
     ema_decay: Optional[float] = None; use_ema: bool = False
-    lora_r: Optional[int] = None; lora_alpha: Optional[float] = None; lora_target: str = "attn"
+    lora_r: Optional[int] = None; lora_alpha: Optional[float] = None; lora_target: str = "attn"; lora_backward: Optional[str] = None
     extra: dict = field(default_factory=dict)
 
 
@@ -197,13 +200,17 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
 def lora_config(cfg: TrainingConfig):
     """The LoRAConfig the flags ask for, or None.  Raises for what is not built: LoRA with EMA, LoRA on more than one GPU."""
     if cfg.lora_r is None:
-        if cfg.lora_alpha is not None or cfg.lora_target != EXTRA_DEFAULTS["lora_target"]:
-            raise ValueError("--lora_alpha / --lora_target need --lora_r")
+        if cfg.lora_alpha is not None or cfg.lora_target != EXTRA_DEFAULTS["lora_target"] or cfg.lora_backward is not None:
+            raise ValueError("--lora_alpha / --lora_target / --lora_backward need --lora_r")
         return None
     from villandiffusion_amd.lora import LoRAConfig
     lc = LoRAConfig(r=cfg.lora_r, alpha=cfg.lora_alpha, target=cfg.lora_target, seed=cfg.seed)      # ValueError for a rank outside [1, 32]
     if cfg.ema_decay is not None:
         raise ValueError("--lora_r together with --ema_decay is not built")
+    if cfg.lora_backward not in (None, "full", "adapted"):
+        raise ValueError(f"--lora_backward must be 'full' or 'adapted', got {cfg.lora_backward!r}")
+    if cfg.lora_backward == "adapted" and cfg.sde_type == "SDE-VE":
+        raise NotImplementedError("--lora_backward adapted is not built for SDE-VE (NCSN++ forms its weight gradients outside the routed funnel)")
     training = cfg.mode in (MODE_TRAIN, MODE_RESUME, MODE_TRAIN_MEASURE)
     if training and (len(str(cfg.gpu).split(",")) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         raise NotImplementedError("--lora_r on more than one GPU is not built")
@@ -495,7 +502,7 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
     n_batch = (len(dsl) + cfg.batch * world - 1) // (cfg.batch * world)
     trainer = Trainer(model, loss_fn, lr=cfg.learning_rate, total_steps=n_batch * cfg.epoch, warmup_steps=cfg.lr_warmup_steps,
                       grad_accum=cfg.gradient_accumulation_steps, ema=EMAConfig(decay=cfg.ema_decay) if cfg.ema_decay is not None else None,
-                      lora=lora_config(cfg))
+                      lora=lora_config(cfg), lora_backward=cfg.lora_backward)
     start_epoch, step = 0, 0
     if cfg.mode == MODE_RESUME:
         trainer.load_state_dict(torch.load(os.path.join(cfg.ckpt_path, "trainer.pt"), map_location=model.device))

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step / vd_lora_merge / vd_lora_grad: additions only */
+#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step / vd_lora_merge / vd_lora_grad / vd_lora_act_grad / vd_lora_act_grad_ws_floats: additions only */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -465,6 +465,29 @@ int vd_lora_merge(const float* w0, float* w, const int64_t* table, int n_jobs, i
  *            ((c0 + c1) + c2) + c3; the sum is multiplied by s. */
 int vd_lora_grad(const float* g, const int64_t* table, int n_jobs, int64_t total_blocks, const float* ab, float* gab, int r, float s,
                  int accumulate, void* stream);
+/* The adapter gradient of 1x1 layers y_b = W x_b (W = W0 + s B A) straight from their activations: no [M, L] weight gradient is formed.
+ *   gab.A[q][l] (+)= s * sum_{b,p} (sum_m Bm[m][q] dy[b][m][p]) x[b][l][p]      gab.B[m][q] (+)= s * sum_{b,p} dy[b][m][p] (sum_l A[q][l] x[b][l][p])
+ * One compute launch plus one reduce launch serve an ACTIVATION JOB TABLE of n_rows x 16 int64, given twice: `host_table` in host memory (every
+ * row is checked there before any launch) and `table`, the same bytes in device memory.  A row is
+ *   {dy address, dy batch stride in floats, x address, x batch stride, images B, M, L, pixels N, offset of A [r, L] in the adapter buffer,
+ *    offset of B [M, r] in the adapter buffer, first workgroup, workgroups n_wg, first accumulator row, accumulator rows, workspace offset in
+ *    floats, first reduce workgroup}
+ * with dy [B, M, N] and x [B, L, N] f32, channel stride N, pixels contiguous (channel slices of wider tensors: their own batch strides).  The
+ * L + M ACCUMULATOR ROWS of a layer are the rows of x (-> A[.][l]) followed by the rows of dy (-> B[m][.]); a table row covers at most 768 of
+ * them, a layer with more takes several table rows (each reads x and dy in full).  1 <= n_wg <= B * ceil(N / 32); first workgroups ascend
+ * from 0 by n_wg, workspace offsets from 0 by n_wg * rows * r, first reduce workgroups from 0 by ceil(rows * r / 256)
+ * (villandiffusion_amd.ops.lora_act_plan lays a table out).  f32 FMA, f32 accumulation, no atomics: bit-reproducible.  The sums:
+ *   workgroup w of a row takes the 32-pixel TILES w, w + n_wg, ... of the B * ceil(N / 32) tiles of its layer (tile = image * ceil(N / 32) +
+ *   tile of the image).  Per tile, Z[q][p] = sum_l A[q][l] x[l][p]: wave v of the four adds the row pairs j = v, v + 4, ... (rows 2j, 2j + 1) in
+ *   that order, one fma chain per row parity; the two parities are added, then the waves as ((w0 + w1) + w2) + w3; T = Bm^T dy likewise.
+ *   Each accumulator element is one fma chain over the pixels of its workgroup's tiles in ascending order (tile after tile), written to the
+ *   workspace; the reduce launch adds the n_wg partials in workgroup order from 0, multiplies by s and stores (accumulate == 0) or adds in f32.
+ * Every pixel is read as a scalar: rows need no alignment, and there is no second path.  ab, x, dy are never written; the padding of gab and
+ * every slot of gab outside the table's rows are never written; `ws` (caller-owned, >= vd_lora_act_grad_ws_floats floats) is scratch.
+ * VD_EINVAL before any launch: a rank outside [1, 32], a row that breaks the rules above, a workspace that is too small. */
+int64_t vd_lora_act_grad_ws_floats(const int64_t* host_table, int n_rows, int r);   /* -1: an invalid table or rank */
+int vd_lora_act_grad(const int64_t* host_table, const int64_t* table, int n_rows, const float* ab, float* gab, int r, float s, int accumulate,
+                     float* ws, int64_t ws_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K9 -- global grad-norm clip + Adam on flat buffers (VillanDiffusion.py:445,1165-1169).

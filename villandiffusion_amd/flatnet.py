@@ -197,6 +197,9 @@ class FlatParamNet(nn.Module):
     _dx_only = True
     G = Gq = _NoGrads()
 
+    def wants_wgrad(self, dw2d) -> bool:
+        return False
+
     def wgrad(self, *args, **kwargs):
         return None
 

@@ -108,6 +108,8 @@ PROTOTYPES = {
     "vd_neuron_step": (_i32, [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i32, _vp]),
     "vd_lora_merge": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _f32, _vp]),
     "vd_lora_grad": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _f32, _i32, _vp]),
+    "vd_lora_act_grad_ws_floats": (_i64, [_vp, _i32, _i32]),
+    "vd_lora_act_grad": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _f32, _i32, _vp, _i64, _vp]),
     "vd_l2norm_sq": (_i32, [_vp, _i64, _vp, _vp, _vp]),
     "vd_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
     "vd_adam_ema_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp]),

@@ -12,14 +12,17 @@ ordinary weight gradient G in `flat_grad`:
       dL/dB = s * G A^T,       dL/dA = s * B^T G.
 
 Two kernels do it, each ONE launch for the whole network over an adapter table built once on the host (`adapter_table`): `vd_lora_merge` and
-`vd_lora_grad`.  No convolution, GroupNorm or attention kernel is touched, and the backward still forms every weight gradient: LoRA here buys
-small, portable checkpoints and a rank constraint, not step time.
+`vd_lora_grad`.  No convolution, GroupNorm or attention kernel is touched, and by default (backward="full") the backward still forms every weight
+gradient.  backward="adapted" (`BackwardRoute`) routes every weight gradient of `UNet2DModel`'s explicit backward instead: a tensor without an
+adapter gets none (nor its bias and GroupNorm sums), an adapted 1x1 layer gets its (dA, dB) straight from the activations (`vd_lora_act_grad`),
+and only the other adapted layers still form G in `flat_grad` for `vd_lora_grad`.
 
 The adapter lives in one flat f32 buffer per network (per job A, then B, every piece at a multiple of 4 floats, padding zero), its gradient in a
 mirror of it, so the global-norm kernel and the Adam kernel serve the whole adapter in one launch each.  Single process; one rank for all layers.
 """
 from __future__ import annotations
 
+import bisect
 import json
 import math
 import os
@@ -31,11 +34,15 @@ import torch
 
 from . import ops
 
-__all__ = ["LoRAConfig", "AdapterTable", "adapter_table", "LoRAAdapter", "LoRAAdam", "TARGETS", "MAX_RANK"]
+__all__ = ["LoRAConfig", "AdapterTable", "adapter_table", "LoRAAdapter", "LoRAAdam", "TARGETS", "MAX_RANK", "BACKWARDS", "backward_routes",
+           "BackwardRoute"]
 
 TARGETS = ("attn", "conv", "all")
+BACKWARDS = ("full", "adapted")
 MAX_RANK = 32
 _ATTN = re.compile(r"(^|\.)attentions\.\d+\.(to_q|to_k|to_v|to_out\.0)\.weight$")
+_DIRECT = re.compile(r"(^|\.)(attentions\.\d+\.(to_q|to_k|to_v|to_out\.0)|conv_shortcut)\.weight$")
+_TEMB = re.compile(r"(^time_embedding\.linear_[12]|\.time_emb_proj)\.weight$")
 TILE = 256                                               # columns of a column workgroup of vd_lora_grad
 
 
@@ -182,15 +189,120 @@ def _target_modules(tab: AdapterTable) -> List[str]:
     return sorted({"to_out.0" if _layer(n).endswith(".to_out.0") else _layer(n).rsplit(".", 1)[-1] for n in tab.slices})
 
 
+# ----------------------------------------------------------------------------------------------------------------------- the adapted backward
+def _check_backward(model, backward: str):
+    """The refusals of backward=..., before the device is touched."""
+    if backward not in BACKWARDS:
+        raise ValueError(f"LoRA: backward must be one of {BACKWARDS}, got {backward!r}")
+    if backward == "adapted" and not getattr(model, "_lora_adapted_backward", False):
+        raise NotImplementedError(f"LoRA backward='adapted' is not built for {type(model).__name__} (its weight gradients bypass UNet2DModel.wgrad); "
+                                  f"use backward='full'")
+
+
+def backward_routes(model, tab: AdapterTable) -> dict:
+    """How backward="adapted" treats the jobs of `tab` on `model` (a UNet2DModel; pure host code): {"direct": names whose (dA, dB) come straight
+    from the activations -- the 1x1 layers whose weight gradient UNet2DModel queues as a plain product of two f32 images: the attention projections
+    and `conv_shortcut`; "full": the other adapted layers, which keep G in flat_grad and vd_lora_grad; "temb": whether the time-embedding MLP's
+    backward still runs (one of its weights has an adapter)}.  Every other parameter of the network gets no gradient at all."""
+    direct = [n for n in tab.slices if _DIRECT.search(n)]
+    full = [n for n in tab.slices if not _DIRECT.search(n)]
+    return {"direct": direct, "full": full, "temb": any(_TEMB.search(n) for n in full)}
+
+
+class BackwardRoute:
+    """What `UNet2DModel.lora_route` holds in adapted mode: the routing of `backward_routes` by flat-gradient offset, the queue of direct jobs of
+    the running backward pass and the launch that serves them (`flush`, called from the network's weight-gradient flush, on its side stream when
+    there is one).  Direct jobs ACCUMULATE into `gab` (the adapter's gradient buffer): `LoRAAdapter.zero_grad` clears it."""
+
+    def __init__(self, model, tab: AdapterTable, ab: torch.Tensor, gab: torch.Tensor):
+        routes = backward_routes(model, tab)
+        self.table, self.ab, self.gab, self.temb = tab, ab, gab, routes["temb"]
+        by_name = dict(zip(tab.slices, tab.jobs))
+        self.direct = {by_name[n][0]: by_name[n] for n in routes["direct"]}          # weight offset -> job
+        self.direct_offs = sorted(self.direct)
+        self.full_offs = {by_name[n][0] for n in routes["full"]}
+        self.full_names = routes["full"]
+        self.full_table = self._sub_table(tab, routes["full"]) if routes["full"] else None
+        self.jobs: list = []                                                          # (job row, dy, x) of the running pass
+        self._plans: Dict[tuple, "ops.ActPlan"] = {}
+        self.ws: Optional[torch.Tensor] = None
+
+    @staticmethod
+    def _sub_table(tab: AdapterTable, names) -> AdapterTable:
+        """The jobs of `names` as a table of their own over the SAME adapter buffer (vd_lora_grad's workgroup columns renumbered)."""
+        by_name = dict(zip(tab.slices, tab.jobs))
+        jobs, rb, cb = [], 0, 0
+        for n in names:
+            off, M, L, aoff, boff, _, _ = by_name[n]
+            jobs.append((off, M, L, aoff, boff, rb, cb))
+            rb += (M + 3) // 4
+            cb += (L + TILE - 1) // TILE
+        return AdapterTable(jobs, {n: tab.slices[n] for n in names}, tab.numel, tab.r, tab.s, [], {n: tab.shapes[n] for n in names}, tab.target)
+
+    def wants(self, net, dw2d) -> bool:
+        """Does the gradient view `dw2d` hold an adapted tensor (full or direct)?"""
+        off = (dw2d.data_ptr() - net.flat_grad.data_ptr()) // 4
+        if off in self.full_offs:
+            return True
+        return bisect.bisect_left(self.direct_offs, off) < bisect.bisect_left(self.direct_offs, off + dw2d.numel())
+
+    def take(self, net, dy, x, dw2d, mode) -> bool:
+        """Route one weight gradient of the running backward pass.  True: nothing more to do for it (no adapter: skipped; direct: queued here).
+        False: the full route -- the caller forms G in flat_grad as ever."""
+        from .lib import B_PLAIN
+        off = (dw2d.data_ptr() - net.flat_grad.data_ptr()) // 4
+        if off in self.full_offs:
+            return False
+        rows, ln = dw2d.shape
+        lo = bisect.bisect_left(self.direct_offs, off)
+        hi = bisect.bisect_left(self.direct_offs, off + rows * ln)
+        for joff in self.direct_offs[lo:hi]:                                          # (the fused q, k, v gradient holds three adapters)
+            _, M, L, aoff, boff, _, _ = self.direct[joff]
+            if (mode != B_PLAIN or isinstance(dy, ops.PreSplit) or isinstance(x, ops.PreSplit) or L != ln or (joff - off) % ln
+                    or (joff - off) // ln + M > rows):
+                raise RuntimeError(f"LoRA adapted backward: the layer at flat offset {joff} is routed direct but its weight gradient is no plain "
+                                   f"product of two f32 images (mode {mode}, [{rows}, {ln}] at {off})")
+            Bn, Cy, H, W, dbs = ops._img(dy)
+            Bx, Cx, Hx, Wx, xbs = ops._img(x)
+            assert (Bx, Cx, Hx * Wx, Cy) == (Bn, L, H * W, rows), (x.shape, dy.shape, dw2d.shape)
+            m0 = (joff - off) // ln
+            self.jobs.append(((dy.data_ptr() + 4 * m0 * H * W, dbs, x.data_ptr(), xbs, Bn, M, L, H * W, aoff, boff), dy, x))
+        return True
+
+    def flush(self, device):
+        """One vd_lora_act_grad launch over the direct jobs queued so far (on the current stream); -> the jobs, whose operands the caller keeps
+        referenced until that stream is joined."""
+        jobs, self.jobs = self.jobs, []
+        if not jobs:
+            return jobs
+        key = tuple(j[0] for j in jobs)
+        plan = self._plans.get(key)
+        if plan is None:                                                              # steady-state training repeats the addresses
+            if len(self._plans) > 64:
+                self._plans.clear()
+            plan = self._plans[key] = ops.lora_act_plan(key, self.table.r)
+        if self.ws is None or self.ws.numel() < plan.ws_floats:
+            self.ws = torch.empty(max(plan.ws_floats, 1 << 20), device=device, dtype=torch.float32)
+        ops.lora_act_grad(plan, self.ab, self.gab, self.table.s, self.ws, accumulate=True)
+        return jobs
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------ the adapter
 class LoRAAdapter:
     """The adapter of one network: `base` (a clone of `flat_param` at construction: W0 and every frozen parameter), `param` and `grad` (the flat
     adapter buffers) and the table.  A ~ U(+-1/sqrt(L)) (torch's kaiming_uniform_(a=sqrt(5)) on [r, L]) drawn on the host in table order from
-    cfg.seed, B = 0: the adapted network starts as the base.  As a context manager it un-merges on exit, also after an exception."""
+    cfg.seed, B = 0: the adapted network starts as the base.  As a context manager it un-merges on exit, also after an exception.
 
-    def __init__(self, model, cfg: LoRAConfig):
+    backward: "full" -- the network forms every weight gradient and `backward_()` reads (dA, dB) off flat_grad; "adapted" -- the network's
+    `lora_route` is set (see `BackwardRoute`): direct layers accumulate into `grad` during each backward pass, `backward_()` writes the slots of
+    the full-route layers from flat_grad and leaves the others alone, so `zero_grad()` belongs where `model.zero_grad()` is called.  Either way
+    `grad` is the whole adapter gradient after `loss.backward(); adapter.backward_()`.  The mode belongs to the run: no state records it.
+    `detach()` takes the route off the network again."""
+
+    def __init__(self, model, cfg: LoRAConfig, backward: str = "full"):
+        _check_backward(model, backward)
         self.table = adapter_table(model, cfg)                # every check before the device is touched
-        self.model, self.cfg = model, cfg
+        self.model, self.cfg, self.backward = model, cfg, backward
         host = self._init_host(self.table, cfg)
         if model.device.type != "cpu":
             from . import lib
@@ -199,6 +311,21 @@ class LoRAAdapter:
         self.base = model.flat_param.detach().clone()
         self.param = host.to(dev)
         self.grad = torch.zeros_like(self.param)
+        self.route = None
+        if backward == "adapted":
+            self.route = model.lora_route = BackwardRoute(model, self.table, self.param, self.grad)
+
+    def detach(self):
+        """Take this adapter's route off the network: its backward forms every weight gradient again."""
+        if self.route is not None and getattr(self.model, "lora_route", None) is self.route:
+            self.model.lora_route = None
+
+    def zero_grad(self):
+        """grad <- 0 (one launch).  Adapted mode accumulates the direct layers' gradients into it during every backward pass."""
+        if self.grad.device.type == "cpu":
+            self.grad.zero_()
+        else:
+            ops.scale_(self.grad, 0.0)
 
     @staticmethod
     def _init_host(tab: AdapterTable, cfg: LoRAConfig) -> torch.Tensor:
@@ -225,8 +352,12 @@ class LoRAAdapter:
         self._weights_written()
 
     def backward_(self, accumulate: bool = False):
-        """grad (+)= the gradient of (A, B) from the weight gradients in model.flat_grad (one launch)."""
-        ops.lora_grad(self.model.flat_grad, self.table, self.param, self.grad, accumulate=accumulate)
+        """grad (+)= the gradient of (A, B) from the weight gradients in model.flat_grad (one launch).  Adapted mode: over the full-route layers
+        only (no launch when there is none); the direct layers' slots already hold their gradient."""
+        if self.route is None:
+            ops.lora_grad(self.model.flat_grad, self.table, self.param, self.grad, accumulate=accumulate)
+        elif self.route.full_table is not None:
+            ops.lora_grad(self.model.flat_grad, self.route.full_table, self.param, self.grad, accumulate=accumulate)
 
     def __enter__(self):
         self.merge_()

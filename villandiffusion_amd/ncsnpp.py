@@ -146,6 +146,7 @@ class NCSNppModel(UNet2DModel):
     # Off for the class: forward() and the autograd function treat the network as they always have (parameter gradients only, a frozen network
     # takes the no-grad forward).  `with net.input_gradients():` switches THIS instance to UNet2DModel's four-case logic (defense_ve does).
     _input_grad = False
+    _lora_adapted_backward = False                            # (the ops.conv_wgrad calls of this backward bypass wgrad(): LoRA backward="full" only)
 
     def __init__(self, in_channels=3, out_channels=3, sample_size=32, block_out_channels=(128, 256, 256, 256),
                  down_block_types=("SkipDownBlock2D", "AttnSkipDownBlock2D", "SkipDownBlock2D", "SkipDownBlock2D"),

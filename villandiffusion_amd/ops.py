@@ -1182,6 +1182,68 @@ def lora_grad(g, tab, ab, gab, accumulate=False):
     return gab
 
 
+ACT_TILE, ACT_CHUNK, ACT_COLS = 32, 768, 16      # pixels of a tile, accumulator rows of a table row, int64 of a table row (vd_lora_act_grad)
+
+
+class ActPlan:
+    """An ACTIVATION JOB TABLE of vd_lora_act_grad laid out on the host (`host`, [n_rows, 16] int64), its workspace floats and algorithmic bytes;
+    `table(device)` is the device copy, uploaded once (after the capture when one is open)."""
+
+    def __init__(self, rows, r, nbytes):
+        self.host = torch.tensor(rows, dtype=torch.int64).view(-1, ACT_COLS).contiguous()
+        self.n_rows, self.r, self.nbytes = self.host.shape[0], int(r), float(nbytes)
+        self.ws_floats = int(L.load().vd_lora_act_grad_ws_floats(self.host.data_ptr(), self.n_rows, self.r))
+        if self.ws_floats < 0:
+            raise L.VillanHipError(f"lora_act_plan: the library refuses the table (rank {r}, {self.n_rows} rows)")
+        self.workgroups = int(self.host[:, 11].sum())
+        self._dev = None
+
+    def table(self, device):
+        if self._dev is None:
+            self._dev = upload_table(self.host, device)
+        elif _CAPTURE_TABLES is not None:
+            _CAPTURE_TABLES.append(self._dev)
+        return self._dev
+
+
+def lora_act_plan(jobs, r, workgroups=512) -> ActPlan:
+    """jobs: (dy address, dy batch stride, x address, x batch stride, B, M, L, N, offset of A, offset of B) per layer, dy [B, M, N] and x [B, L, N]
+    f32 with channel stride N.  A layer of more than 768 accumulator rows (L + M) becomes several table rows.  `workgroups` are shared out in
+    proportion to the bytes a table row reads (at least one, at most one per 32-pixel tile), so that one launch fills the chip."""
+    rows = []
+    for dy, dbs, x, xbs, Bn, M, Ln, N, aoff, boff in jobs:
+        for row0 in range(0, Ln + M, ACT_CHUNK):
+            rows.append([dy, dbs, x, xbs, Bn, M, Ln, N, aoff, boff, 0, 0, row0, min(ACT_CHUNK, Ln + M - row0), 0, 0])
+    if not rows:
+        raise ValueError("lora_act_plan: no jobs")
+    cost = [float(t[4] * t[7] * (t[5] + t[6])) for t in rows]
+    total = sum(cost) or 1.0
+    wg = ws = rb = 0
+    for t, c in zip(rows, cost):
+        tiles = t[4] * ((t[7] + ACT_TILE - 1) // ACT_TILE)
+        t[11] = max(1, min(tiles, int(round(workgroups * c / total))))
+        t[10], t[14], t[15] = wg, ws, rb
+        wg += t[11]
+        ws += t[11] * t[13] * r
+        rb += (t[13] * r + 255) // 256
+    return ActPlan(rows, r, 4.0 * sum(j[4] * j[7] * (j[5] + j[6]) for j in jobs))
+
+
+def lora_act_grad(plan: ActPlan, ab, gab, s, ws, accumulate=False):
+    """gab.A (+)= s (B^T dy) x^T and gab.B (+)= s dy (A x)^T for every job of `plan`, straight from the activations (vd_lora_act_grad: one compute
+    launch and one fixed-order reduce launch; bit-reproducible; slots of gab outside the plan's jobs and its padding are left alone)."""
+    assert ab.is_contiguous() and gab.is_contiguous() and ws.is_contiguous() and ab.dtype == gab.dtype == ws.dtype == torch.float32
+    assert ab.data_ptr() != gab.data_ptr() and ab.device == gab.device == ws.device
+    need = int(torch.maximum(plan.host[:, 8] + plan.r * plan.host[:, 6], plan.host[:, 9] + plan.host[:, 5] * plan.r).max())
+    assert ab.numel() >= need and gab.numel() >= need, (ab.numel(), gab.numel(), need)
+    lib = _lib()
+    table = plan.table(ab.device)
+    _timed("lora_act_grad (lora_act_grad_kernel+lora_act_reduce_kernel)", plan.nbytes, "hbm", lambda: L.check(
+        lib.vd_lora_act_grad(plan.host.data_ptr(), _p(table), plan.n_rows, _p(ab), _p(gab), plan.r, float(s), int(bool(accumulate)), _p(ws),
+                             ws.numel(), _s()), "vd_lora_act_grad"))
+    return gab
+
+
 def l2norm_sq(g, partial, out_sq):
     assert g.is_contiguous() and partial.numel() >= 1024
     _timed("l2norm_sq (sumsq_kernel)", 4.0 * g.numel(), "hbm",

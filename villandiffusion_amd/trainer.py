@@ -171,6 +171,8 @@ class GraphedMicroStep:
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         keep = net.flat_grad.clone()
+        route = getattr(net, "lora_route", None)          # LoRA's adapted backward accumulates into the adapter's gradient buffer as well
+        keep_ad = route.gab.clone() if route is not None else None
         with torch.cuda.stream(side):                     # warm-up off the capture: workspaces, job tables, packed operands, allocator pools
             for _ in range(2):
                 self._body()
@@ -179,6 +181,9 @@ class GraphedMicroStep:
         if _DEBUG:
             print("[graph] warm-up done", flush=True)
         net.flat_grad.copy_(keep)                         # the warm-up passes accumulated gradients: undo
+        if route is not None:
+            route.gab.copy_(keep_ad)
+        self._route_ws = route.ws if route is not None else None      # (the direct kernel's workspace: its address is baked into the capture)
         self._keep = (ops.gemm_ws_buffer(dev, 0), ops._WG_WS.get(dev), getattr(net, "_packed", None), net.wgrad_ws, getattr(net, "_packed16", None),
                       ops.gemm_ws_buffer(dev, ops.AUX_WS_SLOT))      # (the auxiliary stream's workspace: its address is baked into the capture too)
         self.graph = torch.cuda.CUDAGraph()
@@ -194,12 +199,15 @@ class GraphedMicroStep:
 
     def _key(self):
         n = self.net
-        return (n.conv_math, n.wgrad_stream, n.group_wgrad, n.flat_param.data_ptr(), n.flat_grad.data_ptr(), self.trainer.loss_fn.grad_scale)
+        route = getattr(n, "lora_route", None)
+        return (n.conv_math, n.wgrad_stream, n.group_wgrad, n.flat_param.data_ptr(), n.flat_grad.data_ptr(), self.trainer.loss_fn.grad_scale,
+                None if route is None else (id(route), route.gab.data_ptr()))
 
     def valid(self) -> bool:
         dev = self.net.device
         return (self.key == self._key() and self._keep[0] is ops.gemm_ws_buffer(dev, 0) and self._keep[1] is ops._WG_WS.get(dev)
-                and self._keep[3] is self.net.wgrad_ws and self._keep[5] is ops.gemm_ws_buffer(dev, ops.AUX_WS_SLOT))
+                and self._keep[3] is self.net.wgrad_ws and self._keep[5] is ops.gemm_ws_buffer(dev, ops.AUX_WS_SLOT)
+                and self._route_ws is getattr(getattr(self.net, "lora_route", None), "ws", None))
 
     def _body(self):
         net, lf = self.net, self.trainer.loss_fn
@@ -232,10 +240,14 @@ class GraphedMicroStep:
 class Trainer:
     def __init__(self, model, loss_fn, lr: float, total_steps: int, warmup_steps: int = 500, grad_accum: int = 1,
                  max_grad_norm: Optional[float] = 1.0, n_allreduce_buckets: int = 4, graph_micro_step: Optional[bool] = None,
-                 force_ddp_path: bool = False, ema: Optional[EMAConfig] = None, lora=None):
+                 force_ddp_path: bool = False, ema: Optional[EMAConfig] = None, lora=None, lora_backward: Optional[str] = None):
+        """lora_backward (with lora only; None means "full"): "full" -- the backward forms every weight gradient; "adapted" -- only what the
+        adapter needs (lora.BackwardRoute; UNet2DModel).  The mode belongs to the run: no state records it, a state of either loads in both."""
         self.model, self.loss_fn = model, loss_fn
         self.base_lr = lr
         self.adapter = None
+        if lora is None and lora_backward is not None:
+            raise ValueError(f"Trainer: lora_backward={lora_backward!r} needs lora=LoRAConfig(...)")
         if lora is not None:
             # LoRA fine-tune (lora.py): the weights are frozen in a clone, the optimiser owns the flat adapter buffer alone, and every optimiser
             # step ends by writing the merged weights back into flat_param.  Every check comes before the first launch.
@@ -247,7 +259,7 @@ class Trainer:
             if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
                 raise NotImplementedError("Trainer: lora in a process group of more than one rank is not built (the adapter gradient is formed "
                                           "from the local flat_grad)")
-            self.adapter = LoRAAdapter(model, lora)
+            self.adapter = LoRAAdapter(model, lora, backward="full" if lora_backward is None else lora_backward)
             self.opt = LoRAAdam(self.adapter, lr, max_grad_norm=max_grad_norm)
         else:
             self.opt = FusedAdam(model, lr, max_grad_norm=max_grad_norm, ema=ema)
@@ -280,6 +292,12 @@ class Trainer:
         if self.ddp_path:
             model.bucket_ready_hook = self._bucket_ready      # overlap the all-reduce with the rest of backward
         model.zero_grad()
+        self._zero_adapter_grad()
+
+    def _zero_adapter_grad(self):
+        """The adapted backward accumulates the direct layers' gradients into adapter.grad: cleared wherever flat_grad is."""
+        if self.adapter is not None and self.adapter.route is not None:
+            self.adapter.zero_grad()
 
     def _bucket_ready(self, i: int):
         """Called from the UNet's explicit backward when gradient bucket i is final (order: up|out, mid, down, temb)."""
@@ -393,6 +411,7 @@ class Trainer:
             self.sched_step += 1
             self._check_scale()
             self.model.zero_grad()
+            self._zero_adapter_grad()
         return loss
 
     def _graphed(self, batch, timesteps, noise, target_key, poison_key):

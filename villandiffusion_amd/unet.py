@@ -211,22 +211,27 @@ class _Conv:
         weight-gradient stream -- and the input gradient reads `dout_ps` when it is there."""
         net = self.net
         dout_f32 = dout                                       # (the bias gradient's row sums read the f32 tensor)
+        gw = net.G[self.prefix + ".weight"].view(self.cout, self.cin * 9)
+        want = net.wants_wgrad(gw)                            # False: no weight gradient for this tensor, so no pack pass for it either
         if isinstance(x, ops.PreSplit):
-            dy_ps = dout_ps if dout_ps is not None else net.pack_later(dout)
-            net.wgrad(dy_ps, x, net.G[self.prefix + ".weight"].view(self.cout, self.cin * 9), self.mode, pad=self.pad, math_mode=1)
+            if want:
+                dy_ps = dout_ps if dout_ps is not None else net.pack_later(dout)
+                net.wgrad(dy_ps, x, gw, self.mode, pad=self.pad, math_mode=1)
             if dout_ps is not None:
                 dout = dout_ps                                # the input gradient copies (hi, lo) units too
         elif (self.mode == B_CONV3_UP and getattr(net, "presplit", False) and _pairs(net) and net.group_wgrad
               and dout.shape[2] == dout.shape[3] and ops.wgrad_presplit_ok(dout.shape[0], self.cin, self.cout, dout.shape[3], B_CONV3_UP)):
             # Upsample2D's convolution: its input is a block output (f32), so the image is packed on the weight-gradient stream -- two small passes
             # off the critical path for the LDS-DMA kernel (the 256 -> 256 layer at 32x32 outputs is 0.42 ms per step on the converting kernel)
-            dy_ps = dout_ps if dout_ps is not None else net.pack_later(dout)
-            net.wgrad(dy_ps, net.pack_later(x), net.G[self.prefix + ".weight"].view(self.cout, self.cin * 9), self.mode, pad=self.pad, math_mode=1)
+            if want:
+                dy_ps = dout_ps if dout_ps is not None else net.pack_later(dout)
+                net.wgrad(dy_ps, net.pack_later(x), gw, self.mode, pad=self.pad, math_mode=1)
         else:
             assert dout is not None
             bx3 = _split(net) and ops.wgrad_bx3_eligible(self.cout, self.cin, dout.shape[2], dout.shape[3],
                                                                                            self.mode) and x.stride(0) % 4 == 0
-            net.wgrad(dout, x, net.G[self.prefix + ".weight"].view(self.cout, self.cin * 9), self.mode, pad=self.pad, math_mode=int(bx3))
+            if want:
+                net.wgrad(dout, x, gw, self.mode, pad=self.pad, math_mode=int(bx3))
         if not skip_bias:
             B = dout.shape[0]
             ws = bias_ws if bias_ws is not None else net.scratch_bc(B, self.cout)
@@ -703,6 +708,12 @@ class UNet2DModel(FlatParamNet):
     # backward is the input-gradient pass, see _run_backward).  Subclasses with a backward of their own switch it off.
     _input_grad = True
     _dx_only = False                                          # True inside an input-gradient pass: wgrad / rowsum / colsum_later / pack_later queue nothing
+    # LoRA's adapted backward (lora.BackwardRoute, installed by LoRAAdapter(backward="adapted")): routes every weight gradient by the offset of its
+    # tensor in flat_grad -- no adapter: nothing is queued for it (nor any bias / GroupNorm-parameter sum); an adapted plain 1x1 product: (dA, dB)
+    # straight from the activations, queued on the route; any other adapted tensor: as ever.  None: every gradient is formed.
+    lora_route = None
+    _lora_adapted_backward = True                             # (subclasses whose weight gradients bypass wgrad() switch it off)
+    lora_flush_jobs = 8                                       # direct jobs queued before they are launched beside the rest of the pass
 
     def __init__(self, in_channels=3, out_channels=3, sample_size=32, block_out_channels=(128, 256, 256, 256),
                  down_block_types=("DownBlock2D", "AttnDownBlock2D", "DownBlock2D", "DownBlock2D"),
@@ -921,7 +932,7 @@ class UNet2DModel(FlatParamNet):
 
     def colsum_later(self, ws, out, B, Cc, ld=None):
         """out[c] += sum_b ws[b*ld + c], executed at the next _cs_flush() (ws must stay untouched until then)."""
-        if self._dx_only:
+        if self._dx_only or self.lora_route is not None:      # (biases and GroupNorm parameters never have adapters)
             return
         ld = Cc if ld is None else ld
         wp, op = ws.data_ptr(), out.data_ptr()
@@ -933,8 +944,19 @@ class UNet2DModel(FlatParamNet):
     # to fill the chip and moves 32 partial copies of dW through memory.  The gradients of one bucket are independent of each other
     # and off the critical path of the backward pass, so they are queued (operands kept alive) and run as a few grouped launches when
     # the bucket is final.
+    def wants_wgrad(self, dw2d) -> bool:
+        """Will wgrad() do anything for the gradient view `dw2d`?  (No: an input-gradient pass, or an adapted backward and no adapter in it.)"""
+        if self._dx_only:
+            return False
+        return self.lora_route is None or self.lora_route.wants(self, dw2d)
+
     def wgrad(self, dy, x, dw2d, mode, pad=0, math_mode=0):
         if self._dx_only:
+            return
+        route = self.lora_route
+        if route is not None and route.take(self, dy, x, dw2d, mode):
+            if self.wgrad_stream and self.lora_flush_jobs and len(route.jobs) >= self.lora_flush_jobs:
+                self._lora_flush()                            # (the direct jobs alone: the grouped weight gradients keep their own rhythm)
             return
         if math_mode == 1 and self.group_wgrad:
             d = ops.wgrad_desc(dy, x, dw2d, mode, None, accumulate=True, pad=pad, math_mode=1)
@@ -997,13 +1019,30 @@ class UNet2DModel(FlatParamNet):
         ride there too (x is a dY of a queued weight gradient or is kept referenced like one)."""
         if self._dx_only:
             return
+        route = self.lora_route
+        if route is not None and not (route.temb and self._in_d_temb(ws)):
+            return                                            # its only reader was a bias sum (the time-embedding rows: kept with that backward)
         if self.wgrad_stream and self.group_wgrad:
             self._rs_jobs.append((x, ws, ws_ld))
         else:
             ops.rowsum(x, ws, ws_ld=ws_ld)
 
+    def _in_d_temb(self, ws) -> bool:
+        return any(t.data_ptr() <= ws.data_ptr() < t.data_ptr() + 4 * t.numel() for t in self._d_temb.values())
+
+    def _lora_flush(self):
+        """The direct jobs queued so far as one launch on the weight-gradient side stream, operands kept referenced until the join."""
+        if self._wg_side is None:
+            self._wg_side = torch.cuda.Stream(device=self._dev)
+        self._wg_side.wait_stream(torch.cuda.current_stream(self._dev))
+        with torch.cuda.stream(self._wg_side):
+            done = self.lora_route.flush(self._dev)
+        self._wg_keep.append(("direct", done))
+
     def _wg_flush(self):
-        if not any(self._wg_jobs.values()) and not self._rs_jobs and not self._pk_jobs:
+        route = self.lora_route
+        direct = route is not None and bool(route.jobs)
+        if not any(self._wg_jobs.values()) and not self._rs_jobs and not self._pk_jobs and not direct:
             return
         if self.wgrad_stream:
             # Weight gradients are off the critical path of the backward pass: run the grouped launches on a SIDE stream so that they
@@ -1022,7 +1061,8 @@ class UNet2DModel(FlatParamNet):
                 for cls, jobs in self._wg_jobs.items():
                     if jobs:
                         ops.conv_wgrad_group([j[0] for j in jobs], self._dev)
-            self._wg_keep.append((self._wg_jobs, self._rs_jobs, self._pk_jobs))
+                done = route.flush(self._dev) if direct else None
+            self._wg_keep.append((self._wg_jobs, self._rs_jobs, self._pk_jobs, done))
             self._rs_jobs, self._pk_jobs = [], []
         else:
             for t, out in self._pk_jobs:
@@ -1031,6 +1071,8 @@ class UNet2DModel(FlatParamNet):
             for cls, jobs in self._wg_jobs.items():
                 if jobs:
                     ops.conv_wgrad_group([j[0] for j in jobs], self._dev)
+            if direct:
+                route.flush(self._dev)
         self._wg_jobs = {}
 
     def _wg_join(self):
@@ -1103,6 +1145,8 @@ class UNet2DModel(FlatParamNet):
         if self._wg_keep:
             self._wg_join()
         self._wg_jobs, self._rs_jobs, self._pk_jobs = {}, [], []
+        if self.lora_route is not None:
+            self.lora_route.jobs = []
         if self._wt_buf is None:
             self._wt_buf = torch.empty(self._wt_total, device=self._dev, dtype=torch.float32)
         self._wt_fresh = set()
@@ -1392,6 +1436,10 @@ class UNet2DModel(FlatParamNet):
         self._cs_flush()                                          # d_temb_all's partials may sit on the side stream
         if hook is not None:
             hook(2)
+        if self.lora_route is not None and not self.lora_route.temb:
+            if hook is not None:                                  # no weight of the time-embedding MLP has an adapter: it is not differentiated
+                hook(3)
+            return dx_in
         # ---- time embedding backward ----
         emb_sin, e1, e1a, emb, emb_act = st.temb_saved
         d = st.d_temb_all
