@@ -308,6 +308,14 @@ int vd_groupnorm_bwd_fused(const float* dy, const float* x, const float* mean, c
                            float* dbeta_ws, float* rowsum, int B, int C, int HW, int G, int apply_silu,
                            int64_t dy_bstride, int64_t x_bstride, int64_t extra_bstride, int64_t extra2_bstride,
                            int64_t dx_bstride, int64_t rowsum_ld, float* ws, void* stream);
+/* Host-only query (launches nothing): the kernel(s) that `which` (0 vd_groupnorm_fwd, 1 vd_groupnorm_bwd_fused, 2 vd_groupnorm_stats) takes
+ * for these dimensions, chosen by the very functions the entry points switch on.  aligned: every pointer is 16-byte aligned and every
+ * batch stride a multiple of 4 floats; has_ws: ws != NULL; stream: the stream of the call (a capturing stream takes the two-launch chunked
+ * form).  Writes the names as `nm -C` shows the kernels, joined by '+' when there are two launches ("gn_fwd_wave_kernel<2>",
+ * "gn_chunk_stats_kernel<16>+gn_chunk_apply_kernel"); a chunked backward with rowsum adds gn_chunk_rowsum_kernel, a generic one with
+ * extra2 / rowsum the vd_add_strided / vd_rowsum kernels.  Returns the chunks per group S of the chunked kernels, 0 for the others, or
+ * VD_EINVAL (empty name) where the entry point refuses the dimensions. */
+int vd_groupnorm_plan(int which, int B, int C, int HW, int G, int aligned, int has_ws, void* stream, char* name, int name_len);
 
 /* ------------------------------------------------------------------------------------------
  * K4 -- attention softmax.  S is [nb][N][N] stored key-major: S[b][j][i] = k_j . q_i * scale;

@@ -183,7 +183,7 @@ def test_linear_family():
 @pytest.mark.parametrize("B,C,H,silu", [(4, 128, 32, True), (2, 384, 32, True), (3, 256, 16, False), (8, 512, 4, True), (5, 256, 4, True),
                                         (2, 512, 8, True),
                                         (2, 256, 32, True),          # 8 K-element groups: the 512-thread backward (as (2, 384, 32): 12 K)
-                                        # groups of > 12 K elements: the multi-workgroup (chunked) kernels
+                                        # groups of 256 K / 128 K elements: the multi-workgroup (chunked) kernels; 16 K elements: register-resident, <7, 1024>
                                         (1, 128, 256, True), (2, 256, 128, True), (2, 128, 64, False),
                                         # 14 336- and 28 672-element groups (config #5's 32x32 / 64x64 levels): register-resident with 512 / 1024 threads
                                         (2, 448, 32, True), (1, 224, 64, True), (2, 192, 64, False)])
@@ -218,7 +218,8 @@ def test_groupnorm_silu(B, C, H, silu):
     check(dg, gamma.grad, 3e-5, "groupnorm dgamma")
     check(db, beta.grad, 3e-5, "groupnorm dbeta")
     # vd_groupnorm_bwd_fused: a second residual gradient (a channel slice of a wider buffer, like a skip connection's) and the per-image
-    # channel sums of the dx written (rows of a wider matrix) from the same pass; every kernel family (register-resident, chunked, generic)
+    # channel sums of the dx written (rows of a wider matrix) from the same pass, on the one-wave, register-resident and chunked kernels (the generic
+    # kernels and the remaining instantiations: test_groupnorm_edges_gpu.py)
     e2buf = torch.randn(B, C + 64, H, H, generator=g(5)).to(DEV)
     e2 = e2buf[:, 64:]
     rs = torch.full((B, C + 8), -7.0, device=DEV)

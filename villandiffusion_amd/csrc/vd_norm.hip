@@ -1092,6 +1092,77 @@ static int gn_chunk1_capacity() {
     return best;
 }
 
+// ---- kernel choice: one function per entry point, shared by the launch and by vd_groupnorm_plan() (which launches nothing) ----
+enum GnFwdKernel {      // vd_groupnorm_fwd and vd_groupnorm_stats
+    GN_F_CHUNK1_16, GN_F_CHUNK1_8, GN_F_CHUNK2_16, GN_F_CHUNK2_8, GN_F_WAVE1, GN_F_WAVE2, GN_F_WAVE4, GN_F_REG1, GN_F_REG2, GN_F_REG4, GN_F_REG8,
+    GN_F_REG12, GN_F_REG7_512, GN_F_REG7_1024, GN_F_GENERIC
+};
+enum GnBwdKernel {      // vd_groupnorm_bwd_fused
+    GN_B_WAVE1, GN_B_WAVE2, GN_B_WAVE4, GN_B_REG1_256, GN_B_REG2_256, GN_B_REG4_256, GN_B_REG4_512, GN_B_REG6_512, GN_B_REG7_512, GN_B_REG7_1024,
+    GN_B_CHUNK1_16, GN_B_CHUNK1_8, GN_B_CHUNK2, GN_B_GENERIC
+};
+static const char* const GN_FWD_NAMES[] = {
+    "gn_chunk1_fwd_kernel<16>", "gn_chunk1_fwd_kernel<8>", "gn_chunk_stats_kernel<16>+gn_chunk_apply_kernel", "gn_chunk_stats_kernel<8>+gn_chunk_apply_kernel",
+    "gn_fwd_wave_kernel<1>", "gn_fwd_wave_kernel<2>", "gn_fwd_wave_kernel<4>", "gn_fwd_reg_kernel<1, 256>", "gn_fwd_reg_kernel<2, 256>",
+    "gn_fwd_reg_kernel<4, 256>", "gn_fwd_reg_kernel<8, 256>", "gn_fwd_reg_kernel<12, 256>", "gn_fwd_reg_kernel<7, 512>", "gn_fwd_reg_kernel<7, 1024>",
+    "gn_fwd_kernel"};
+static const char* const GN_BWD_NAMES[] = {
+    "gn_bwd_wave_kernel<1>", "gn_bwd_wave_kernel<2>", "gn_bwd_wave_kernel<4>", "gn_bwd_reg_kernel<1, 256>", "gn_bwd_reg_kernel<2, 256>",
+    "gn_bwd_reg_kernel<4, 256>", "gn_bwd_reg_kernel<4, 512>", "gn_bwd_reg_kernel<6, 512>", "gn_bwd_reg_kernel<7, 512>", "gn_bwd_reg_kernel<7, 1024>",
+    "gn_chunk1_bwd_kernel<16>", "gn_chunk1_bwd_kernel<8>", "gn_chunk_bwd_stats_kernel+gn_chunk_bwd_apply_kernel", "gn_bwd_kernel"};
+
+// the register-resident forward / statistics kernel of an aligned slab of at most GN_REG_MAX elements
+static GnFwdKernel gn_fwd_reg_choice(int64_t slab) {
+    if (slab <= 1024 && gn_wave_ok()) return slab <= 256 ? GN_F_WAVE1 : slab <= 512 ? GN_F_WAVE2 : GN_F_WAVE4;
+    if (slab <= 1024) return GN_F_REG1;
+    if (slab <= 2048) return GN_F_REG2;
+    if (slab <= 4096) return GN_F_REG4;
+    if (slab <= 8192) return GN_F_REG8;
+    if (slab <= 12 * 1024) return GN_F_REG12;
+    if (slab <= 14 * 1024) return GN_F_REG7_512;
+    return GN_F_REG7_1024;
+}
+
+// al: every pointer 16-byte aligned and every batch stride a multiple of 4 floats.  S: chunks per group of the chunked kernels, else 0.
+static GnFwdKernel gn_fwd_choice(int B, int C, int HW, int G, bool al, bool has_ws, hipStream_t st, int* S_out) {
+    const int64_t slab = (int64_t)(C / G) * HW;
+    al = al && HW % 4 == 0;
+    const int S = (al && has_ws) ? gn_chunks(B, C, HW, G, true) : 0;
+    *S_out = S;
+    if (S && gn_chunk1_ok(st, S)) return slab / S > 8192 ? GN_F_CHUNK1_16 : GN_F_CHUNK1_8;
+    if (S) return slab / S > 8192 ? GN_F_CHUNK2_16 : GN_F_CHUNK2_8;
+    if (al && slab <= GN_REG_MAX) return gn_fwd_reg_choice(slab);
+    return GN_F_GENERIC;
+}
+
+static GnBwdKernel gn_bwd_choice(int B, int C, int HW, int G, bool al, bool has_ws, hipStream_t st, int* S_out) {
+    const int64_t slab = (int64_t)(C / G) * HW;
+    const int L = HW / 4;
+    const int S = (al && has_ws) ? gn_chunks(B, C, HW, G) : 0;
+    *S_out = S;
+    const bool reg_ok = !S && al && HW % 4 == 0 && slab <= GN_REG_MAX &&
+                        ((L >= 64 && L % 64 == 0) || (L < 64 && (L & (L - 1)) == 0 && L > 0));
+    if (reg_ok) {
+        if (slab <= 1024 && L < 64 && gn_wave_ok()) return slab <= 256 ? GN_B_WAVE1 : slab <= 512 ? GN_B_WAVE2 : GN_B_WAVE4;
+        if (slab <= 1024) return GN_B_REG1_256;
+        if (slab <= 2048) return GN_B_REG2_256;
+        if (slab <= 4096) return GN_B_REG4_256;
+        if (slab <= 8192) return GN_B_REG4_512;
+        if (slab <= 12 * 1024) return GN_B_REG6_512;
+        if (slab <= 14 * 1024) return GN_B_REG7_512;
+        return GN_B_REG7_1024;
+    }
+    // (gn_chunks cuts backward chunks of at most 8192 floats, so <16> is never taken today: tests/test_gn_ref_cpu.py lists it as unreachable)
+    if (S && gn_chunk1_ok(st, S)) return slab / S > 8192 ? GN_B_CHUNK1_16 : GN_B_CHUNK1_8;
+    if (S) return GN_B_CHUNK2;
+    return GN_B_GENERIC;
+}
+
+static bool gn_dims_ok(int B, int C, int HW, int G) { return B > 0 && C > 0 && HW > 0 && G > 0 && C % G == 0; }
+static bool gn_stats_dims_ok(int B, int C, int HW, int G) { return gn_dims_ok(B, C, HW, G) && C / G <= 256; }
+static bool gn_stats_slab_ok(int C, int HW, int G, bool al) { return HW % 4 == 0 && al && (int64_t)(C / G) * HW <= GN_REG_MAX; }
+static bool gn_bwd_dims_ok(int B, int C, int HW, int G) { return gn_dims_ok(B, C, HW, G) && C / G <= 64; }
+
 // a timeout reported by an earlier polling launch fails every later GroupNorm call until vd_async_errors(1) clears it
 int gn_sticky_impl(const char* who) {
     const unsigned n = gn_flag_read();
@@ -1124,57 +1195,54 @@ extern "C" int vd_groupnorm_fwd(const float* x, const float* gamma, const float*
                                 float* ws, void* stream) {
     VD_REQUIRE(x && gamma && beta && y && mean && rstd, "vd_groupnorm_fwd: null pointer");
     VD_REQUIRE(B > 0 && C > 0 && HW > 0 && G > 0 && C % G == 0, "vd_groupnorm_fwd: bad dims B=%d C=%d HW=%d G=%d", B, C, HW, G);
-    const int64_t slab = (int64_t)(C / G) * HW;
-    const bool al = (HW % 4 == 0) && (x_bstride % 4 == 0) && (y_bstride % 4 == 0) && ((((uintptr_t)x) & 15) == 0) &&
-                    ((((uintptr_t)y) & 15) == 0);
-    const bool reg_ok = al && slab <= GN_REG_MAX;
-    const int S = (al && ws) ? gn_chunks(B, C, HW, G, true) : 0;
+    const bool al = (x_bstride % 4 == 0) && (y_bstride % 4 == 0) && ((((uintptr_t)x) & 15) == 0) && ((((uintptr_t)y) & 15) == 0);
     if (const int rc = vd_gn_sticky("vd_groupnorm_fwd")) return rc;
-    if (S && gn_chunk1_ok((hipStream_t)stream, S)) {       // one launch: the chunk stays in registers between statistics and apply
-        unsigned long long* words = reinterpret_cast<unsigned long long*>(ws + 4 * (int64_t)B * G * S);
-        unsigned* flag = gn_flag_dev();
-        if (slab / S > 8192)
-            hipLaunchKernelGGL((gn_chunk1_fwd_kernel<16>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, words, C, HW,
-                               G, S, eps, apply_silu, x_bstride, y_bstride, gn_next_epoch(), flag, gn_poll_max());
-        else
-            hipLaunchKernelGGL((gn_chunk1_fwd_kernel<8>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, words, C, HW,
-                               G, S, eps, apply_silu, x_bstride, y_bstride, gn_next_epoch(), flag, gn_poll_max());
-        VD_LAUNCH_CHECK("vd_groupnorm_fwd");
-        return 0;
-    }
-    if (S) {       // large slabs: S workgroups per group (partials in ws, vd_groupnorm_ws_floats())
-        if (slab / S > 8192) hipLaunchKernelGGL((gn_chunk_stats_kernel<16>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, x, ws, C, HW, G, S, x_bstride);
-        else hipLaunchKernelGGL((gn_chunk_stats_kernel<8>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, x, ws, C, HW, G, S, x_bstride);
-        hipLaunchKernelGGL(gn_chunk_apply_kernel, dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd,
-                           ws, C, HW, G, S, eps, apply_silu, x_bstride, y_bstride);
-        VD_LAUNCH_CHECK("vd_groupnorm_fwd");
-        return 0;
-    }
-#define VD_GN_FWD(NVV)                                                                                                       \
-    hipLaunchKernelGGL((gn_fwd_reg_kernel<NVV>), dim3(B * G), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, \
-                       C, HW, G, eps, apply_silu, x_bstride, y_bstride, (float*)nullptr)
-    if (reg_ok && slab <= 1024 && gn_wave_ok()) {
+    int S = 0;
+    const GnFwdKernel k = gn_fwd_choice(B, C, HW, G, al, ws != nullptr, (hipStream_t)stream, &S);
+#define VD_GN_CHUNK1(NVV)                                                                                                                           \
+    hipLaunchKernelGGL((gn_chunk1_fwd_kernel<NVV>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd,              \
+                       reinterpret_cast<unsigned long long*>(ws + 4 * (int64_t)B * G * S), C, HW, G, S, eps, apply_silu, x_bstride, y_bstride,      \
+                       gn_next_epoch(), flag, gn_poll_max())
+#define VD_GN_CHUNK2(NVV)                                                                                                                           \
+    do {                                                                                                                                            \
+        hipLaunchKernelGGL((gn_chunk_stats_kernel<NVV>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, x, ws, C, HW, G, S, x_bstride);        \
+        hipLaunchKernelGGL(gn_chunk_apply_kernel, dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, ws, C, HW, G,  \
+                           S, eps, apply_silu, x_bstride, y_bstride);                                                                               \
+    } while (0)
 #define VD_GN_FWDW(NVV)                                                                                                                     \
     hipLaunchKernelGGL((gn_fwd_wave_kernel<NVV>), dim3(vd_cdiv(B * G, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, \
                        C, HW, G, eps, apply_silu, x_bstride, y_bstride, (float*)nullptr, B * G)
-        if (slab <= 256) VD_GN_FWDW(1);
-        else if (slab <= 512) VD_GN_FWDW(2);
-        else VD_GN_FWDW(4);
-#undef VD_GN_FWDW
-    } else if (reg_ok && slab <= 1024) VD_GN_FWD(1);
-    else if (reg_ok && slab <= 2048) VD_GN_FWD(2);
-    else if (reg_ok && slab <= 4096) VD_GN_FWD(4);
-    else if (reg_ok && slab <= 8192) VD_GN_FWD(8);
-    else if (reg_ok && slab <= 12 * 1024) VD_GN_FWD(12);
-    else if (reg_ok && slab <= 14 * 1024)
-        hipLaunchKernelGGL((gn_fwd_reg_kernel<7, 512>), dim3(B * G), dim3(512), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, C, HW, G, eps,
-                           apply_silu, x_bstride, y_bstride, (float*)nullptr);
-    else if (reg_ok)
-        hipLaunchKernelGGL((gn_fwd_reg_kernel<7, 1024>), dim3(B * G), dim3(1024), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, C, HW, G, eps,
-                           apply_silu, x_bstride, y_bstride, (float*)nullptr);
-    else
+#define VD_GN_FWD(NVV, NT)                                                                                                          \
+    hipLaunchKernelGGL((gn_fwd_reg_kernel<NVV, NT>), dim3(B * G), dim3(NT), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, \
+                       C, HW, G, eps, apply_silu, x_bstride, y_bstride, (float*)nullptr)
+    switch (k) {
+    case GN_F_CHUNK1_16:       // one launch: the chunk stays in registers between statistics and apply
+    case GN_F_CHUNK1_8: {
+        unsigned* flag = gn_flag_dev();
+        if (k == GN_F_CHUNK1_16) VD_GN_CHUNK1(16);
+        else VD_GN_CHUNK1(8);
+        break;
+    }
+    case GN_F_CHUNK2_16: VD_GN_CHUNK2(16); break;       // large slabs: S workgroups per group (partials in ws, vd_groupnorm_ws_floats())
+    case GN_F_CHUNK2_8: VD_GN_CHUNK2(8); break;
+    case GN_F_WAVE1: VD_GN_FWDW(1); break;
+    case GN_F_WAVE2: VD_GN_FWDW(2); break;
+    case GN_F_WAVE4: VD_GN_FWDW(4); break;
+    case GN_F_REG1: VD_GN_FWD(1, 256); break;
+    case GN_F_REG2: VD_GN_FWD(2, 256); break;
+    case GN_F_REG4: VD_GN_FWD(4, 256); break;
+    case GN_F_REG8: VD_GN_FWD(8, 256); break;
+    case GN_F_REG12: VD_GN_FWD(12, 256); break;
+    case GN_F_REG7_512: VD_GN_FWD(7, 512); break;
+    case GN_F_REG7_1024: VD_GN_FWD(7, 1024); break;
+    case GN_F_GENERIC:
         hipLaunchKernelGGL(gn_fwd_kernel, dim3(B * G), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, C, HW, G,
                            eps, apply_silu, x_bstride, y_bstride);
+        break;
+    }
+#undef VD_GN_CHUNK1
+#undef VD_GN_CHUNK2
+#undef VD_GN_FWDW
 #undef VD_GN_FWD
     VD_LAUNCH_CHECK("vd_groupnorm_fwd");
     return 0;
@@ -1183,32 +1251,29 @@ extern "C" int vd_groupnorm_fwd(const float* x, const float* gamma, const float*
 extern "C" int vd_groupnorm_stats(const float* x, const float* gamma, const float* beta, float* ss, float* mean, float* rstd, int B,
                                   int C, int HW, int G, float eps, int64_t x_bstride, void* stream) {
     VD_REQUIRE(x && gamma && beta && ss && mean && rstd, "vd_groupnorm_stats: null pointer");
-    VD_REQUIRE(B > 0 && C > 0 && HW > 0 && G > 0 && C % G == 0 && C / G <= 256, "vd_groupnorm_stats: bad dims");
+    VD_REQUIRE(gn_stats_dims_ok(B, C, HW, G), "vd_groupnorm_stats: bad dims");
     const int64_t slab = (int64_t)(C / G) * HW;
-    VD_REQUIRE(HW % 4 == 0 && x_bstride % 4 == 0 && ((((uintptr_t)x) & 15) == 0) && slab <= GN_REG_MAX,
+    VD_REQUIRE(gn_stats_slab_ok(C, HW, G, x_bstride % 4 == 0 && ((((uintptr_t)x) & 15) == 0)),
                "vd_groupnorm_stats: needs 16-B aligned groups of at most 28672 elements (got %lld)", (long long)slab);
-#define VD_GN_ST(NVV)                                                                                                          \
-    hipLaunchKernelGGL((gn_fwd_reg_kernel<NVV>), dim3(B * G), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (float*)nullptr, \
-                       mean, rstd, C, HW, G, eps, 0, x_bstride, (int64_t)0, ss)
-    if (slab <= 1024 && gn_wave_ok()) {                           // (the same kernel as vd_groupnorm_fwd takes for this slab: identical statistics)
 #define VD_GN_STW(NVV)                                                                                                                       \
     hipLaunchKernelGGL((gn_fwd_wave_kernel<NVV>), dim3(vd_cdiv(B * G, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (float*)nullptr, \
                        mean, rstd, C, HW, G, eps, 0, x_bstride, (int64_t)0, ss, B * G)
-        if (slab <= 256) VD_GN_STW(1);
-        else if (slab <= 512) VD_GN_STW(2);
-        else VD_GN_STW(4);
+#define VD_GN_ST(NVV, NT)                                                                                                          \
+    hipLaunchKernelGGL((gn_fwd_reg_kernel<NVV, NT>), dim3(B * G), dim3(NT), 0, (hipStream_t)stream, x, gamma, beta, (float*)nullptr, \
+                       mean, rstd, C, HW, G, eps, 0, x_bstride, (int64_t)0, ss)
+    switch (gn_fwd_reg_choice(slab)) {                            // (the same kernel as vd_groupnorm_fwd takes for this slab: identical statistics)
+    case GN_F_WAVE1: VD_GN_STW(1); break;
+    case GN_F_WAVE2: VD_GN_STW(2); break;
+    case GN_F_WAVE4: VD_GN_STW(4); break;
+    case GN_F_REG1: VD_GN_ST(1, 256); break;
+    case GN_F_REG2: VD_GN_ST(2, 256); break;
+    case GN_F_REG4: VD_GN_ST(4, 256); break;
+    case GN_F_REG8: VD_GN_ST(8, 256); break;
+    case GN_F_REG12: VD_GN_ST(12, 256); break;
+    case GN_F_REG7_512: VD_GN_ST(7, 512); break;
+    default: VD_GN_ST(7, 1024); break;
+    }
 #undef VD_GN_STW
-    } else if (slab <= 1024) VD_GN_ST(1);
-    else if (slab <= 2048) VD_GN_ST(2);
-    else if (slab <= 4096) VD_GN_ST(4);
-    else if (slab <= 8192) VD_GN_ST(8);
-    else if (slab <= 12 * 1024) VD_GN_ST(12);
-    else if (slab <= 14 * 1024)
-        hipLaunchKernelGGL((gn_fwd_reg_kernel<7, 512>), dim3(B * G), dim3(512), 0, (hipStream_t)stream, x, gamma, beta, (float*)nullptr, mean, rstd, C,
-                           HW, G, eps, 0, x_bstride, (int64_t)0, ss);
-    else
-        hipLaunchKernelGGL((gn_fwd_reg_kernel<7, 1024>), dim3(B * G), dim3(1024), 0, (hipStream_t)stream, x, gamma, beta, (float*)nullptr, mean, rstd, C,
-                           HW, G, eps, 0, x_bstride, (int64_t)0, ss);
 #undef VD_GN_ST
     VD_LAUNCH_CHECK("vd_groupnorm_stats");
     return 0;
@@ -1271,60 +1336,49 @@ extern "C" int vd_groupnorm_bwd_fused(const float* dy, const float* x, const flo
                                       int64_t x_bstride, int64_t extra_bstride, int64_t extra2_bstride, int64_t dx_bstride,
                                       int64_t rowsum_ld, float* ws, void* stream) {
     VD_REQUIRE(dy && x && mean && rstd && gamma && beta && dx && dgamma_ws && dbeta_ws, "vd_groupnorm_bwd: null pointer");
-    VD_REQUIRE(B > 0 && C > 0 && HW > 0 && G > 0 && C % G == 0 && C / G <= 64, "vd_groupnorm_bwd: bad dims");
+    VD_REQUIRE(gn_bwd_dims_ok(B, C, HW, G), "vd_groupnorm_bwd: bad dims");
     VD_REQUIRE(!rowsum || rowsum_ld >= C, "vd_groupnorm_bwd: rowsum_ld < C");
     if (const int rc = vd_gn_sticky("vd_groupnorm_bwd")) return rc;
-    const int64_t slab = (int64_t)(C / G) * HW;
-    const int L = HW / 4;
     const bool al = ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx) | ((uintptr_t)extra) | ((uintptr_t)extra2)) & 15) == 0 &&
                     ((x_bstride | dy_bstride | dx_bstride | extra_bstride | extra2_bstride) & 3) == 0;
-    const int S = (al && ws) ? gn_chunks(B, C, HW, G) : 0;
-    const bool reg_ok = !S && al && HW % 4 == 0 && slab <= GN_REG_MAX &&
-                        ((L >= 64 && L % 64 == 0) || (L < 64 && (L & (L - 1)) == 0 && L > 0));
-    if (reg_ok) {
+    int S = 0;
+    const GnBwdKernel k = gn_bwd_choice(B, C, HW, G, al, ws != nullptr, (hipStream_t)stream, &S);
 #define VD_GN_BWD(NVV, NT)                                                                                                          \
     hipLaunchKernelGGL((gn_bwd_reg_kernel<NVV, NT>), dim3(B * G), dim3(NT), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, beta, \
                        extra, dx, dgamma_ws, dbeta_ws, C, HW, G, apply_silu, dy_bstride, x_bstride, extra_bstride, dx_bstride,      \
                        extra2, extra2_bstride, rowsum, rowsum_ld)
-        if (slab <= 1024 && L < 64 && gn_wave_ok()) {
 #define VD_GN_BWDW(NVV)                                                                                                                          \
     hipLaunchKernelGGL((gn_bwd_wave_kernel<NVV>), dim3(vd_cdiv(B * G, 4)), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, beta, extra, \
                        dx, dgamma_ws, dbeta_ws, C, HW, G, apply_silu, dy_bstride, x_bstride, extra_bstride, dx_bstride, extra2, extra2_bstride,   \
                        rowsum, rowsum_ld, B * G)
-            if (slab <= 256) VD_GN_BWDW(1);
-            else if (slab <= 512) VD_GN_BWDW(2);
-            else VD_GN_BWDW(4);
-#undef VD_GN_BWDW
-        } else if (slab <= 1024) VD_GN_BWD(1, 256);
-        else if (slab <= 2048) VD_GN_BWD(2, 256);
-        else if (slab <= 4096) VD_GN_BWD(4, 256);
-        else if (slab <= 8192) VD_GN_BWD(4, 512);
-        else if (slab <= 12 * 1024) VD_GN_BWD(6, 512);
-        else if (slab <= 14 * 1024) VD_GN_BWD(7, 512);
-        else VD_GN_BWD(7, 1024);
-#undef VD_GN_BWD
-        VD_LAUNCH_CHECK("vd_groupnorm_bwd");
-        return 0;
-    }
-    if (S && gn_chunk1_ok((hipStream_t)stream, S)) {
+#define VD_GN_BCHUNK1(NVV)                                                                                                                          \
+    hipLaunchKernelGGL((gn_chunk1_bwd_kernel<NVV>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, beta, extra, dx,  \
+                       dgamma_ws, dbeta_ws, words, C, HW, G, S, apply_silu, dy_bstride, x_bstride, extra_bstride, dx_bstride, extra2,              \
+                       extra2_bstride, rs_part, gn_next_epoch(), flag, gn_poll_max())
+    switch (k) {
+    case GN_B_WAVE1: VD_GN_BWDW(1); break;
+    case GN_B_WAVE2: VD_GN_BWDW(2); break;
+    case GN_B_WAVE4: VD_GN_BWDW(4); break;
+    case GN_B_REG1_256: VD_GN_BWD(1, 256); break;
+    case GN_B_REG2_256: VD_GN_BWD(2, 256); break;
+    case GN_B_REG4_256: VD_GN_BWD(4, 256); break;
+    case GN_B_REG4_512: VD_GN_BWD(4, 512); break;
+    case GN_B_REG6_512: VD_GN_BWD(6, 512); break;
+    case GN_B_REG7_512: VD_GN_BWD(7, 512); break;
+    case GN_B_REG7_1024: VD_GN_BWD(7, 1024); break;
+    case GN_B_CHUNK1_16:
+    case GN_B_CHUNK1_8: {
         unsigned* flag = gn_flag_dev();
         float* rs_part = rowsum ? ws + 2 * (int64_t)B * G * S : nullptr;
         unsigned long long* words = reinterpret_cast<unsigned long long*>(ws + 4 * (int64_t)B * G * S);
-        if (slab / S > 8192)
-            hipLaunchKernelGGL((gn_chunk1_bwd_kernel<16>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, beta, extra, dx,
-                               dgamma_ws, dbeta_ws, words, C, HW, G, S, apply_silu, dy_bstride, x_bstride, extra_bstride, dx_bstride, extra2,
-                               extra2_bstride, rs_part, gn_next_epoch(), flag, gn_poll_max());
-        else
-            hipLaunchKernelGGL((gn_chunk1_bwd_kernel<8>), dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, beta, extra, dx,
-                               dgamma_ws, dbeta_ws, words, C, HW, G, S, apply_silu, dy_bstride, x_bstride, extra_bstride, dx_bstride, extra2,
-                               extra2_bstride, rs_part, gn_next_epoch(), flag, gn_poll_max());
+        if (k == GN_B_CHUNK1_16) VD_GN_BCHUNK1(16);
+        else VD_GN_BCHUNK1(8);
         if (rowsum)
             hipLaunchKernelGGL(gn_chunk_rowsum_kernel, dim3(vd_cdiv(B * C, 256)), dim3(256), 0, (hipStream_t)stream, rs_part, rowsum, B, C, G, S,
                                rowsum_ld);
-        VD_LAUNCH_CHECK("vd_groupnorm_bwd");
-        return 0;
+        break;
     }
-    if (S) {
+    case GN_B_CHUNK2: {
         hipLaunchKernelGGL(gn_chunk_bwd_stats_kernel, dim3(B * G * S), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma,
                            beta, ws, C, HW, G, S, apply_silu, dy_bstride, x_bstride);
         float* rs_part = rowsum ? ws + 2 * (int64_t)B * G * S : nullptr;
@@ -1334,13 +1388,18 @@ extern "C" int vd_groupnorm_bwd_fused(const float* dy, const float* x, const flo
         if (rowsum)
             hipLaunchKernelGGL(gn_chunk_rowsum_kernel, dim3(vd_cdiv(B * C, 256)), dim3(256), 0, (hipStream_t)stream, rs_part, rowsum, B, C, G, S,
                                rowsum_ld);
-        VD_LAUNCH_CHECK("vd_groupnorm_bwd");
-        return 0;
-    } else {
+        break;
+    }
+    case GN_B_GENERIC:
         hipLaunchKernelGGL(gn_bwd_kernel, dim3(B * G), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, beta, extra, dx,
                            dgamma_ws, dbeta_ws, C, HW, G, apply_silu, dy_bstride, x_bstride, extra_bstride, dx_bstride);
+        break;
     }
+#undef VD_GN_BWD
+#undef VD_GN_BWDW
+#undef VD_GN_BCHUNK1
     VD_LAUNCH_CHECK("vd_groupnorm_bwd");
+    if (k != GN_B_GENERIC) return 0;       // extra2 and rowsum rode in the kernel
     if (extra2) {
         const int rc = vd_add_strided(dx, extra2, B, (int64_t)C * HW, dx_bstride, extra2_bstride, 1, stream);
         if (rc) return rc;
@@ -1355,4 +1414,28 @@ extern "C" int vd_groupnorm_bwd(const float* dy, const float* x, const float* me
                                 int64_t extra_bstride, int64_t dx_bstride, float* ws, void* stream) {
     return vd_groupnorm_bwd_fused(dy, x, mean, rstd, gamma, beta, extra, nullptr, dx, dgamma_ws, dbeta_ws, nullptr, B, C, HW, G, apply_silu,
                                   dy_bstride, x_bstride, extra_bstride, 0, dx_bstride, 0, ws, stream);
+}
+
+// Host-only: the kernel(s) the entry point `which` (0 vd_groupnorm_fwd, 1 vd_groupnorm_bwd_fused, 2 vd_groupnorm_stats) launches for these
+// dimensions, from the same choice functions; nothing is launched.
+extern "C" int vd_groupnorm_plan(int which, int B, int C, int HW, int G, int aligned, int has_ws, void* stream, char* name, int name_len) {
+    VD_REQUIRE(name && name_len > 0, "vd_groupnorm_plan: null name buffer");
+    name[0] = 0;
+    VD_REQUIRE(which >= 0 && which <= 2, "vd_groupnorm_plan: which = %d (0 fwd, 1 bwd, 2 stats)", which);
+    const char* nm = nullptr;
+    int S = 0;
+    if (which == 0) {
+        VD_REQUIRE(gn_dims_ok(B, C, HW, G), "vd_groupnorm_fwd: bad dims B=%d C=%d HW=%d G=%d", B, C, HW, G);
+        nm = GN_FWD_NAMES[gn_fwd_choice(B, C, HW, G, aligned != 0, has_ws != 0, (hipStream_t)stream, &S)];
+    } else if (which == 1) {
+        VD_REQUIRE(gn_bwd_dims_ok(B, C, HW, G), "vd_groupnorm_bwd: bad dims");
+        nm = GN_BWD_NAMES[gn_bwd_choice(B, C, HW, G, aligned != 0, has_ws != 0, (hipStream_t)stream, &S)];
+    } else {
+        VD_REQUIRE(gn_stats_dims_ok(B, C, HW, G), "vd_groupnorm_stats: bad dims");
+        VD_REQUIRE(gn_stats_slab_ok(C, HW, G, aligned != 0), "vd_groupnorm_stats: needs 16-B aligned groups of at most 28672 elements (got %lld)",
+                   (long long)((int64_t)(C / G) * HW));
+        nm = GN_FWD_NAMES[gn_fwd_reg_choice((int64_t)(C / G) * HW)];
+    }
+    snprintf(name, (size_t)name_len, "%s", nm);
+    return S;
 }

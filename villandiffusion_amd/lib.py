@@ -81,6 +81,7 @@ PROTOTYPES = {
     "vd_groupnorm_bwd": (_i32, [_vp] * 10 + [_i32] * 5 + [_i64] * 4 + [_vp, _vp]),
     "vd_groupnorm_stats_from_partials": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "vd_groupnorm_bwd_fused": (_i32, [_vp] * 12 + [_i32] * 5 + [_i64] * 6 + [_vp, _vp]),
+    "vd_groupnorm_plan": (_i32, [_i32] * 7 + [_vp, C.c_char_p, _i32]),
     "vd_softmax_col_fwd": (_i32, [_vp, _i32, _i32, _vp]),
     "vd_softmax_col_bwd": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp]),
     "vd_attn_small_fwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i64, _i64, _vp]),

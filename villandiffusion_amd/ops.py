@@ -834,6 +834,22 @@ def _gn_ws(Bn, Cc, HW, G, device):
     return _gemm_ws(need, device) if need > 0 else None
 
 
+GN_FWD, GN_BWD, GN_STATS = 0, 1, 2
+
+
+def groupnorm_plan(which, Bn, Cc, HW, G, aligned=True, has_ws=None, stream=None):
+    """(kernel names, chunks per group) that groupnorm_fwd / groupnorm_bwd / groupnorm_stats (which = GN_FWD / GN_BWD / GN_STATS) take for
+    these dimensions: a host-only query of the library's own dispatch (vd_groupnorm_plan), nothing is launched.  has_ws None: as the
+    wrappers call it (a workspace whenever vd_groupnorm_ws_floats asks for one); stream None: no stream (never capturing)."""
+    lib = L.load()                      # no device needed
+    if has_ws is None:
+        has_ws = lib.vd_groupnorm_ws_floats(Bn, Cc, HW, G) > 0
+    buf = C.create_string_buffer(128)
+    S = lib.vd_groupnorm_plan(which, Bn, Cc, HW, G, int(aligned), int(has_ws), stream, buf, len(buf))
+    L.check(min(S, 0), "vd_groupnorm_plan")
+    return buf.value.decode(), S
+
+
 def groupnorm_fwd(x, gamma, beta, y, mean, rstd, G, eps, silu):
     Bn, Cc, H, W, xbs = _img(x)
     ybs = _img(y)[4]
