@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from villandiffusion_amd import lib as L
 from villandiffusion_amd import ops
-from villandiffusion_amd.lib import B_CONV3, B_CONV3_T, B_CONV3_UP
+from villandiffusion_amd.lib import B_CONV3, B_CONV3_S2, B_CONV3_T, B_CONV3_UP
 
 DEV = "cuda"
 ARITHS = ("bf16x3", "f16", "bf16", "f32")
@@ -75,15 +75,28 @@ def conv_f64(x, w, mode, chunk=16):
     return out
 
 
-def wgrad_f64(dy, x, mode, taps=9, chunk=16):
-    """dW[m, c*9 + t] = sum_{b,p} dy[b,m,p] * im2col(x)[b, c*9 + t, p] in float64 on the GPU."""
-    dy, x = dy.to(DEV).double(), x.to(DEV).double()
+def wgrad_cols(x, mode, taps=9, pad=0):
+    """im2col of x [b, C, H, W] (float64) as the weight gradient contracts it: [b, C * taps, output pixels].  B_CONV3_S2 is the stride-2
+    Downsample2D convolution: pad = 0 pads one zero column on the right and one zero row below (F.pad(x, (0, 1, 0, 1)), no further padding),
+    pad = 1 is padding = 1 on every side.  Images need not be square."""
+    if taps != 9:
+        return x.flatten(2)
+    if mode == B_CONV3_S2:
+        assert pad in (0, 1), pad
+        return F.unfold(F.pad(x, (0, 1, 0, 1)), 3, stride=2) if pad == 0 else F.unfold(x, 3, padding=1, stride=2)
     if mode == B_CONV3_UP:
         x = F.interpolate(x, scale_factor=2.0, mode="nearest")
+    return F.unfold(x, 3, padding=1)
+
+
+def wgrad_f64(dy, x, mode, taps=9, chunk=16, pad=0):
+    """dW[m, c*9 + t] = sum_{b,p} dy[b,m,p] * im2col(x)[b, c*9 + t, p] in float64 on the GPU (im2col: wgrad_cols)."""
+    dy, x = dy.to(DEV).double(), x.to(DEV).double()
     B, M = dy.shape[:2]
+    chunk = max(1, min(chunk, (1 << 25) // max(1, x.shape[1] * taps * dy.shape[2] * dy.shape[3])))      # <= 256 MB of columns at a time
     acc = 0
     for b0 in range(0, B, chunk):
-        cols = F.unfold(x[b0:b0 + chunk], 3, padding=1) if taps == 9 else x[b0:b0 + chunk].flatten(2)
+        cols = wgrad_cols(x[b0:b0 + chunk], mode, taps, pad)
         acc = acc + torch.einsum("bmp,bkp->mk", dy[b0:b0 + chunk].flatten(2), cols)
     return acc
 
@@ -108,9 +121,10 @@ def gemm1x1_f64(x, w, arith, bias=None, residual=None, acc=None):
     return _epilogue(y.view(x.shape[0], w.shape[0], x.shape[2], x.shape[3]), bias, None, residual, acc)
 
 
-def wgrad_arith_f64(dy, x, mode, arith, taps=9, acc=None):
-    """Weight gradient dW [M, C*taps] of a 3x3 (mode B_CONV3 / B_CONV3_UP) or 1x1 (taps = 1) convolution in the given arithmetic."""
-    y = contract(lambda a, b: wgrad_f64(a, b, mode, taps), dy.to(DEV), x.to(DEV), arith)
+def wgrad_arith_f64(dy, x, mode, arith, taps=9, acc=None, pad=0):
+    """Weight gradient dW [M, C*taps] of a 3x3 (mode B_CONV3 / B_CONV3_UP / B_CONV3_S2 with its `pad`) or 1x1 (taps = 1) convolution in the
+    given arithmetic."""
+    y = contract(lambda a, b: wgrad_f64(a, b, mode, taps, pad=pad), dy.to(DEV), x.to(DEV), arith)
     return y if acc is None else y + acc.to(DEV).double()
 
 

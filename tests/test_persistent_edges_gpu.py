@@ -74,13 +74,14 @@ def wgrad_name(kind, S, up, arith):
 
 
 ARITY = {"conv3_k32p_kernel": 7, "conv3_sm_kernel": 5, "gemm1x1_k32p_kernel": 3, "wgrad_ps_group_kernel": 3, "wgrad_k32_group_kernel": 3,
-         "wgrad1x1_wide_group_kernel": 1}
+         "wgrad1x1_wide_group_kernel": 1,
+         "wgrad_bx3_group_kernel": 3, "wgrad_bx3_kernel": 3, "wgrad_k32_kernel": 2}        # (WIDE = false by default; cases: test_wgrad_edges_gpu.py)
 
 
 def normalise(name):
     """An instantiation name as ops records it -> the full template argument list (defaulted arguments are all false), without the
-    '@<width>' and '(+group_reduce)' suffixes."""
-    name = name.replace("(+group_reduce)", "").split("@")[0].strip()
+    '@<width>' and '(+group_reduce)' / '(+slab_reduce)' suffixes."""
+    name = name.replace("(+group_reduce)", "").replace("(+slab_reduce)", "").split("@")[0].strip()
     fam, _, args = name.partition("<")
     args = [a.strip() for a in args.rstrip(">").split(",") if a.strip()]
     return f"{fam}<{', '.join(args + ['false'] * (ARITY[fam] - len(args)))}>"

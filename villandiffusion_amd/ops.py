@@ -716,6 +716,19 @@ def conv_wgrad_group(descs: Sequence[WgradDesc], device):
         nbytes=nbytes)
 
 
+def wgrad_single_name(OW, mode) -> str:
+    """The instantiation vd_conv_wgrad launches for a split-precision (math = 1) 3x3 weight gradient of tile 4 (the switch in vd_gemm.hip): stride 2 and
+    4x4 / wide stride-1 outputs run wgrad_bx3_kernel (32-pixel row segments from 64 pixels up), 8x8 / 16x16 / 32x32 stride-1 outputs wgrad_k32_kernel."""
+    if mode == B_CONV3_S2:
+        return f"wgrad_bx3_kernel<{min(OW, 32)}, 4{', true' if OW >= 64 else ''}>"
+    md = 2 if mode == B_CONV3_UP else 0
+    if OW >= 64:
+        return f"wgrad_bx3_kernel<32, {md}, true>"
+    if OW == 4:
+        return "wgrad_bx3_kernel<4, 0>"
+    return f"wgrad_k32_kernel<{OW}, {md}>"
+
+
 def conv_wgrad(dy, x, dw2d, mode, ws: Optional[torch.Tensor], accumulate=False, splits=0, tile=0, pad=0, math_mode=0):
     """dw2d[M, C*T] (+)= sum_{b,p} dy[b,m,p] * gather_mode(x)[b, c, p(+)t]."""
     d = wgrad_desc(dy, x, dw2d, mode, ws, accumulate, splits, tile, pad, math_mode)
@@ -739,7 +752,7 @@ def conv_wgrad(dy, x, dw2d, mode, ws: Optional[torch.Tensor], accumulate=False, 
     elif tl.value == 5:
         name = "wgrad1x1_bx3_kernel(+slab_reduce)"
     elif tl.value == 4 and math_mode == 1:
-        name = f"wgrad_bx3_kernel<{min(OW, 32)}, {0 if mode == B_CONV3 else 2}{', wide' if OW > 32 else ''}>(+slab_reduce)"
+        name = wgrad_single_name(OW, mode) + "(+slab_reduce)"
     elif tl.value == 4:
         name = f"wgrad_patch_kernel<{OW}, {0 if mode == B_CONV3 else 2}>(+slab_reduce)"
     else:
