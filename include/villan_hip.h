@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 11 /* unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step / vd_lora_merge / vd_lora_grad / vd_lora_act_grad / vd_lora_act_grad_ws_floats: additions only */
+#define VD_ABI_VERSION 12 /* 12: vd_gemm_kernel_name / vd_conv_wgrad_kernel_name / vd_conv_wgrad_group_kernel_name; a refused pool2 problem answers -1 at vd_gemm_tile.  Unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step / vd_lora_merge / vd_lora_grad / vd_lora_act_grad / vd_lora_act_grad_ws_floats: additions only */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -118,7 +118,9 @@ typedef struct vd_gemm_desc {
     int32_t pool2;           /* 1: VD_B_CONV3_T with a_packed at 16x16 / 32x32 outputs only (the input gradient of an Upsample2D convolution):
                                 the epilogue adds each 2x2 block of output pixels and writes D at HALF resolution (ldd = (OH/2)*(OW/2)),
                                 i.e. conv-transpose followed by the adjoint of the nearest-2x upsample, without the full-resolution tensor.
-                                Needs an unsplit grid (M/128 * N/128 >= 256 tiles), no bias / rowadd / residual / accumulate; else VD_EINVAL */
+                                Needs an unsplit grid (ceil(M/128) * ceil(N/128) >= 256 tiles), no bias / rowadd / residual / accumulate; the
+                                persistent kernel (vd_gemm_tile() == 18) also takes it on the wider images it walks.  Else vd_gemm_tile()
+                                answers -1 and vd_gemm VD_EINVAL */
     int32_t kh, kw;          /* VD_B_CONVG only: kernel height / width (K = C*kh*kw)                                    */
     int32_t conv_stride;     /* VD_B_CONVG only: 1 .. 4 (both directions)                                               */
     int32_t pad_h, pad_w;    /* VD_B_CONVG only: zero padding on each side                                              */
@@ -155,6 +157,11 @@ int64_t vd_gemm_ws_floats(const vd_gemm_desc* desc);
  * bias / rowadd / residual / accumulate; its sums run over all channels in one chain, so it agrees with the split kernels (8 / 16) to the path's
  * tolerance, not bit for bit, -1: a_packed given for an unsupported problem (profiling / tests). */
 int vd_gemm_tile(const vd_gemm_desc* desc);
+/* Host-only query (launches nothing, makes no HIP call, needs no device and no workspace): returns vd_gemm_tile(desc) and writes the name of the
+ * kernel vd_gemm would launch -- the instantiation as the profiler prints it, written by the very branch that launches it ("conv3_bx3_kernel<32, 1,
+ * 2, 512, 2>"; the exact-f32 gather kernels as "gemm_kernel<128x128,ROW,CONV3_S2>"; the persistent 3x3 kernel on images wider than 32 pixels with
+ * the image width behind it: "conv3_k32p_kernel<32, 0, true, true, false, false>@64").  Where vd_gemm refuses the descriptor: VD_EINVAL, empty name. */
+int vd_gemm_kernel_name(const vd_gemm_desc* desc, char* name, int name_len);
 
 /* Weight gradient of a 3x3 / 1x1 convolution (K2/K5/K6/K7 backward, deterministic split-K):
  *   dW[m][c*T + t] (+)= sum_{b,p} dY[b][m][p] * gather(X)[b][c][p (+) t]
@@ -190,6 +197,10 @@ int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream);
 int64_t vd_conv_wgrad_ws_floats(const vd_wgrad_desc* desc);
 /* Tile and split count vd_conv_wgrad will use (profiling / tests). */
 int vd_conv_wgrad_plan(const vd_wgrad_desc* desc, int* tile, int* splits);
+/* Host-only query as vd_gemm_kernel_name: returns the tile of vd_conv_wgrad_plan and writes the kernel vd_conv_wgrad would launch, with the reduction
+ * that follows it in brackets ("wgrad_k32_kernel<16, 2>(+slab_reduce)", "wgrad_small_kernel<true>(+colsum)"); VD_EINVAL and an empty name where
+ * vd_conv_wgrad refuses the descriptor. */
+int vd_conv_wgrad_kernel_name(const vd_wgrad_desc* desc, char* name, int name_len);
 
 /* ------------------------------------------------------------------------------------------
  * PRE-SPLIT activation images (round 5, ABI 11) -- csrc/vd_presplit.hip.
@@ -235,6 +246,9 @@ int vd_conv_wgrad_group_variant(int cls);
 int vd_conv_wgrad_group_plan(const vd_wgrad_desc* descs, int n, void* table_out, int64_t* ws_floats, int* blocks, int* rblocks);
 int vd_conv_wgrad_group_rebase(void* dev_table, int n, float* ws, void* stream);
 int vd_conv_wgrad_group_launch(const void* dev_table, int n, int cls, int blocks, int rblocks, void* stream);
+/* Host-only query: the kernel vd_conv_wgrad_group_launch runs for a class ("wgrad_ps_group_kernel<16, 2, true>(+group_reduce)"); 0, or VD_EINVAL
+ * (empty name) for a class the launch has no case for. */
+int vd_conv_wgrad_group_kernel_name(int cls, char* name, int name_len);
 
 /* Split-precision operand for vd_gemm_desc.a_packed.  taps = 9: element (m, c, t) of the logical [M][C][9] matrix of a 3x3
  * convolution is read from W[m*row_stride + c*chan_stride + t] (plain weights: row_stride = C*9, chan_stride = 9; the transposed

@@ -57,7 +57,7 @@ def test_merge_entry_point_in_header_and_ctypes_table():
     assert m, "vd_image_set_merge is not declared in include/villan_hip.h"
     assert "vd_image_set_merge" in lib.PROTOTYPES and len(lib.PROTOTYPES["vd_image_set_merge"][1]) == len(m.group(1).split(",")) == 9
     assert hasattr(lib.load(), "vd_image_set_merge") and callable(ops.image_set_merge)
-    assert re.search(r"#define VD_ABI_VERSION 11\b", hdr) and lib.load().vd_abi_version() == 11
+    assert re.search(r"#define VD_ABI_VERSION 12\b", hdr) and lib.load().vd_abi_version() == 12
 
 
 def test_refusals_fire_before_the_device_is_touched(monkeypatch):

@@ -37,7 +37,7 @@ def test_public_names_and_entry_points():
         assert f"int {name}(" in hdr
         assert name in lib.PROTOTYPES and len(lib.PROTOTYPES[name][1]) == n_args
         assert hasattr(lib.load(), name)
-    assert "#define VD_ABI_VERSION 11" in hdr and lib.load().vd_abi_version() == 11
+    assert "#define VD_ABI_VERSION 12" in hdr and lib.load().vd_abi_version() == 12
     assert callable(ops.score_inv_objective) and callable(ops.pyramid_dgrad)
 
 

@@ -3,6 +3,10 @@ split-precision weight gradients (three: wgrad_bx3_group_kernel, wgrad_bx3_kerne
 library is reached by an edge case: the instantiations are read from the library's host stubs (nm -C), the cases' expected names come from
 the same pure functions the GPU tests check against the names ops records.  A new instantiation without a case fails here.  The tables of
 test_wgrad_edges_gpu.py are also held to the planner regimes they were sized for."""
+import ctypes as C
+import itertools
+import json
+import os
 import re
 import shutil
 import subprocess
@@ -10,11 +14,29 @@ import subprocess
 import pytest
 
 from villandiffusion_amd import lib, ops
-from villandiffusion_amd.lib import B_CONV3, B_CONV3_S2, B_CONV3_UP
+from villandiffusion_amd.lib import B_CONV3, B_CONV3_S2, B_CONV3_UP, B_PLAIN
 import test_persistent_edges_gpu as edges
 import test_wgrad_edges_gpu as wedges
 
 FAMILIES = tuple(edges.ARITY)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kernel_names.json")
+FAKE = 0x10000
+EINVAL = -22          # VD_EINVAL of include/villan_hip.h
+
+
+def lib_name(query, what):
+    """(return value, name) of one of the library's host-only name queries."""
+    buf = C.create_string_buffer(128)
+    rc = getattr(lib.load(), query)(what, buf, len(buf))
+    return rc, buf.value.decode()
+
+
+def gemm_name(d):
+    return lib_name("vd_gemm_kernel_name", C.byref(d))
+
+
+def wgrad_name(d):
+    return lib_name("vd_conv_wgrad_kernel_name", C.byref(d))
 
 
 def _nm():
@@ -58,15 +80,138 @@ def test_the_kernels_that_are_no_templates_are_reached_by_name():
     assert wedges.S1, "no case reaches wgrad1x1_bx3_kernel"
 
 
+def sw_desc(row):
+    _, _, mode, B, Cin, Cout, OH, OW, pad, _ = row
+    return ops.wgrad_query_desc(Cout, Cin, OH, OW, mode, B, pad=pad)
+
+
 def test_the_recorded_single_launch_names_mirror_the_dispatch():
-    """ops.wgrad_single_name against the names the 3x3 single-launch cases expect (written out in their table)."""
+    """The library's name for the 3x3 single-launch cases against the names they expect (written out in their table)."""
     for row in wedges.SW:
-        _, name, mode, _, _, _, _, OW, _, _ = row
-        assert edges.normalise(ops.wgrad_single_name(OW, mode)) == edges.normalise(name), row
-    assert ops.wgrad_single_name(128, B_CONV3_S2) == "wgrad_bx3_kernel<32, 4, true>"
-    assert ops.wgrad_single_name(32, B_CONV3_S2) == "wgrad_bx3_kernel<32, 4>"
-    assert ops.wgrad_single_name(32, B_CONV3_UP) == "wgrad_k32_kernel<32, 2>"
-    assert ops.wgrad_single_name(4, B_CONV3) == "wgrad_bx3_kernel<4, 0>"
+        assert wgrad_name(sw_desc(row)) == (4, row[1] + "(+slab_reduce)"), row
+    for (OW, mode), name in {(128, B_CONV3_S2): "wgrad_bx3_kernel<32, 4, true>", (32, B_CONV3_S2): "wgrad_bx3_kernel<32, 4>",
+                             (32, B_CONV3_UP): "wgrad_k32_kernel<32, 2>", (4, B_CONV3): "wgrad_bx3_kernel<4, 0>"}.items():
+        assert wgrad_name(ops.wgrad_query_desc(128, 128, OW, OW, mode, 4)) == (4, name + "(+slab_reduce)")
+
+
+def test_the_library_names_every_edge_case_as_its_table_expects():
+    """What the GPU edge tests assert of the names ops records, asked of the library's own name queries for each case's descriptor: no GPU."""
+    def flags(opts, arith, ps=False, gn=False):
+        f = {"math": edges.MATH[arith], "b_presplit": int(ps)}
+        f.update({k: FAKE for k, o in (("bias", "bias"), ("rowadd", "rowadd"), ("residual", "res")) if o in opts.split()})
+        f.update(accumulate=int("acc" in opts.split()), pool2=int("pool2" in opts.split()))
+        if gn:
+            f["gn_ss"] = FAKE
+        return f
+
+    for p in edges.k18_cases():
+        row, arith, ps = p.values
+        _, B, Cin, Cout, OH, OW, mode, opts, _ = row
+        d = ops.conv_query_desc(Cout, Cin, OH, OW, edges.MODES[mode][0], B, **flags(opts, arith, ps, mode == "gn"))
+        tile, name = gemm_name(d)
+        assert tile == 18 and edges.normalise(name) == edges.k18_expected(row, arith, ps), (p.id, tile, name)
+        assert name.endswith(f"@{OW}") == (OW > 32), name
+    for p in edges.k20_cases():
+        row, arith = p.values
+        _, B, Cin, Cout, S, mode, opts = row
+        tile, name = gemm_name(ops.conv_query_desc(Cout, Cin, S, S, edges.MODES[mode][0], B, **flags(opts, arith)))
+        assert tile == 20 and edges.normalise(name) == edges.k20_expected(row, arith), (p.id, tile, name)
+    for p in edges.k19_cases():
+        row, arith = p.values
+        _, B, Cin, Cout, S, opts, _ = row
+        d = ops.product_query_desc(Cout, Cin, S * S, B)
+        for k, v in flags(opts, arith).items():
+            setattr(d, k, v)
+        tile, name = gemm_name(d)
+        assert tile == 19 and edges.normalise(name) == edges.k19_expected(row, arith), (p.id, tile, name)
+    for p in edges.wg_cases():
+        row, arith = p.values
+        rc, name = lib_name("vd_conv_wgrad_group_kernel_name", edges.wg_class(row, arith))
+        assert rc == 0 and name.endswith("(+group_reduce)") and edges.normalise(name) == edges.wg_expected(row, arith), (p.id, name)
+    for row in wedges.GW:
+        rc, name = lib_name("vd_conv_wgrad_group_kernel_name", row[1])
+        assert rc == 0 and edges.normalise(name) == wedges.group_name(row[1]), (row[0], name)
+        for B, Cin, Cout, OH, OW, pad in row[3]:          # ... and the class is the one the planner gives the case's jobs
+            d = ops.wgrad_query_desc(Cout, Cin, OH, OW, wedges.CLASS_MODE[row[1]], B, pad=pad)
+            assert lib.load().vd_conv_wgrad_group_class(C.byref(d)) == row[1], (row[0], B, Cin, Cout)
+    for rid, B, Cin, Cout, S, _ in wedges.S1:
+        assert wgrad_name(ops.wgrad_query_desc(Cout, Cin, S, S, B_PLAIN, B)) == (5, "wgrad1x1_bx3_kernel(+slab_reduce)"), rid
+
+
+def golden():
+    """The file with its cases unfolded into g["rows"]: one row per problem (a case lists its problems as cartesian blocks)."""
+    with open(GOLDEN) as f:
+        g = json.load(f)
+    g["rows"] = [dict(case, a=list(args)) for case in g["cases"] for block in case["a"]
+                 for args in itertools.product(*(v if isinstance(v, list) else [v] for v in block))]
+    return g
+
+
+def golden_desc(row):
+    make = {"conv": ops.conv_query_desc, "product": ops.product_query_desc, "wgrad": ops.wgrad_query_desc}[row["q"]]
+    flags = row.get("f", {})
+    if row["q"] == "product":
+        d = make(*row["a"])
+        for k, v in flags.items():
+            setattr(d, k, v)
+        return d
+    return make(*row["a"], **flags)
+
+
+def test_the_library_reproduces_the_recorded_names():
+    """tests/golden/kernel_names.json holds the names the Python name ladders gave before the library took them over (see its header): every
+    problem of the planner sweep of test_cabi.py, the flags the ladders looked at, every grouped class.  String for string, and the tile."""
+    g = golden()
+    assert re.search(r"commit [0-9a-f]{7}", g["header"]["about"])
+    assert os.path.getsize(GOLDEN) < max(os.path.getsize(os.path.join(os.path.dirname(GOLDEN), f)) for f in os.listdir(os.path.dirname(GOLDEN))
+                                         if f != "kernel_names.json")
+    bad = []
+    for row in g["rows"]:
+        rc, name = (wgrad_name if row["q"] == "wgrad" else gemm_name)(golden_desc(row))
+        want = (EINVAL if row["tile"] == -1 else row["tile"], row["name"])
+        if (rc, name) != want:
+            bad.append((row, rc, name))
+    assert not bad, (len(bad), bad[:5])
+    assert len(g["rows"]) > 3000 and any(r["tile"] == -1 and r["f"].get("pool2") and r["a"][:2] == [64, 16] for r in g["rows"])
+    for cls in range(0, 14000):
+        want = g["group"].get(str(cls))
+        assert lib_name("vd_conv_wgrad_group_kernel_name", cls) == ((0, want) if want else (EINVAL, "")), cls
+    assert len(g["group"]) == 33
+    corrected = {(r["corrected_from"].split("<")[0], r["name"].split("<")[0]) for r in g["rows"] if "corrected_from" in r}
+    assert corrected == {("conv3_fewout_kernel", "conv3_smallm_kernel"), ("wgrad_patch_kernel", "wgrad_patch_gen_kernel")}
+    few = [r for r in g["rows"] if r.get("corrected_from", "").startswith("conv3_fewout") and r.get("f", {}).get("B") == 0x10004]
+    assert few, "the unaligned-B direct convolution is asked with a pointer of 0x10004"
+
+
+def test_every_recorded_name_is_an_instantiation_in_the_library():
+    """Every kernel name of the golden sweep, of every family, is a device stub of the built library (trailing defaulted template arguments
+    allowed for); the generic gather kernels, recorded by tile size and enumerator, are matched through their own spelling."""
+    stubs = {}
+    for m in re.finditer(r"__device_stub__(\w+?)(?:<([^>]*)>)?\(", _nm()):
+        stubs.setdefault(m.group(1), set()).add(tuple(a.strip() for a in (m.group(2) or "").split(",") if a.strip()))
+    tiles = {"128x128": ("2", "2"), "64x128": ("1", "2"), "64x64": ("1", "1")}
+    a_modes = {"ROW": "0", "COL": "1"}
+    b_modes = {"PLAIN": "0", "KCONTIG": "1", "CONV3": "2", "CONV3_T": "3", "CONV3_S2": "4", "CONV3_UP": "5", "CONV3_DIL": "6", "CONVG": "7"}
+    g = golden()
+    names = {r["name"] for r in g["rows"] if r["name"]} | set(g["group"].values())
+    assert len(names) > 150
+    for name in sorted(names):
+        name = re.sub(r"\(\+\w+\)$", "", name).split("@")[0]
+        fam, _, args = name.partition("<")
+        args = [a.strip() for a in args.rstrip(">").split(",") if a.strip()]
+        if fam == "gemm_kernel":
+            args = list(tiles[args[0]]) + [a_modes[args[1]], b_modes[args[2]]]
+        elif fam == "wgrad_kernel":
+            args = list(tiles[args[0]]) + [b_modes[args[1]]]
+        assert fam in stubs, f"{name}: no kernel {fam} in the library"
+        assert any(_same(args, stub) for stub in stubs[fam]), (name, sorted(stubs[fam])[:8])
+
+
+def _same(args, stub):
+    """The recorded arguments are the stub's, up to the spelling of booleans and trailing arguments left at their default (false)."""
+    num = {"true": "1", "false": "0"}
+    n = len(args)
+    return [num.get(x, x) for x in stub[:n]] == [num.get(x, x) for x in args] and all(x == "false" for x in stub[n:])
 
 
 def test_the_grouped_table_reaches_every_regime_it_was_sized_for():

@@ -150,7 +150,7 @@ def test_the_mode_belongs_to_the_run_not_to_the_adapter(tmp_path):
 
 def test_header_prototypes_and_abi():
     hdr = open(os.path.join(ROOT, "include", "villan_hip.h")).read()
-    assert "#define VD_ABI_VERSION 11" in hdr and lib.load().vd_abi_version() == 11
+    assert "#define VD_ABI_VERSION 12" in hdr and lib.load().vd_abi_version() == 12
     assert "int vd_lora_act_grad(" in hdr and "int64_t vd_lora_act_grad_ws_floats(" in hdr and "ACTIVATION JOB TABLE" in hdr
     proto = hdr[hdr.index("int vd_lora_act_grad("):]
     proto = proto[:proto.index(";")]

@@ -236,7 +236,7 @@ def test_trainer_refusals_come_before_any_launch():
 
 def test_header_prototypes_and_abi():
     hdr = open(os.path.join(ROOT, "include", "villan_hip.h")).read()
-    assert "#define VD_ABI_VERSION 11" in hdr
+    assert "#define VD_ABI_VERSION 12" in hdr
     for name, n_args in (("vd_lora_merge", 9), ("vd_lora_grad", 10)):
         assert f"int {name}(" in hdr and len(lib.PROTOTYPES[name][1]) == n_args and callable(getattr(ops, name[3:]))
     assert "ADAPTER TABLE" in hdr and "n_jobs x 7 int64" in hdr

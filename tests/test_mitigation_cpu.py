@@ -142,11 +142,11 @@ def test_header_declares_both_entry_points_and_the_wrappers_exist():
         assert len(m.group(1).split(",")) == n_args
         assert name in lib.PROTOTYPES and len(lib.PROTOTYPES[name][1]) == n_args
     assert callable(ops.removal_loss) and callable(ops.image_set_stats)
-    assert re.search(r"#define VD_ABI_VERSION 11\b", hdr)
+    assert re.search(r"#define VD_ABI_VERSION 12\b", hdr)
     mk = open(os.path.join(ROOT, "villandiffusion_amd", "csrc", "Makefile")).read()
     assert "vd_defense.hip" in mk and re.search(r"vd_defense\.o:.*\n\t.*-ffp-contract=off", mk)
 
 
-def test_abi_version_is_still_11():
+def test_abi_version_is_12():
     from villandiffusion_amd import lib
-    assert lib.load().vd_abi_version() == 11
+    assert lib.load().vd_abi_version() == 12

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include "villan_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -28,6 +29,27 @@ int vd_gn_sticky(const char* who);
             vd_set_error("%s: launch failed: %s", name, hipGetErrorString(e__)); \
             return (int)e__;                                                \
         }                                                                   \
+    } while (0)
+
+// One call site per instantiation serves the launch AND the host-only name queries (vd_gemm_kernel_name, vd_conv_wgrad_kernel_name,
+// vd_conv_wgrad_group_kernel_name): with name == NULL this is hipLaunchKernelGGL(K, ...); with a name buffer (char[VD_NAME_LEN]) nothing is launched and
+// K's own text is written -- so K is spelled with EVERY template argument, as the profiler prints the instantiation (parenthesised when it has commas).
+#define VD_NAME_LEN 128
+static inline void vd_name_write(char* name, const char* k) {
+    const int paren = k[0] == '(';
+    int n = (int)strlen(k) - 2 * paren;
+    if (n >= 2 && k[paren + n - 2] == '<' && k[paren + n - 1] == '>') n -= 2;      // "kernel<>" (all arguments defaulted) is recorded as "kernel"
+    snprintf(name, VD_NAME_LEN, "%.*s", n, k + paren);
+}
+static inline int vd_name_append(char* name, const char* suffix) {      // returns 0: `return vd_name_append(...)` ends a name path
+    const size_t n = strlen(name);
+    snprintf(name + n, VD_NAME_LEN - n, "%s", suffix);
+    return 0;
+}
+#define VD_LAUNCH_OR_NAME(name, K, ...)                      \
+    do {                                                     \
+        if (name) vd_name_write(name, #K);                   \
+        else hipLaunchKernelGGL(K, __VA_ARGS__);             \
     } while (0)
 
 // vd_gemm_desc.debug: timing-only ablation bits (wrong results) exist in `make ABLATION=1` builds only; the release library rejects a non-zero value

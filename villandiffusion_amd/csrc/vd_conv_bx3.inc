@@ -803,13 +803,14 @@ static bool gemm_bx3_act_eligible(const vd_gemm_desc& d) {
     return true;
 }
 
-static void launch_gemm_bx3_act(const vd_gemm_desc& d, hipStream_t st) {
+static void launch_gemm_bx3_act(const vd_gemm_desc& d, hipStream_t st, char* name) {
     const dim3 grid(vd_cdiv(d.M, 128) * (d.N / 128));
     const bool adir = d.a_mode == VD_A_ROW, bdir = d.b_mode == VD_B_KCONTIG;
-    if (adir && bdir) hipLaunchKernelGGL((gemm_bx3_act_kernel<true, true>), grid, dim3(NT), 0, st, d);
-    else if (adir) hipLaunchKernelGGL((gemm_bx3_act_kernel<true, false>), grid, dim3(NT), 0, st, d);
-    else if (bdir) hipLaunchKernelGGL((gemm_bx3_act_kernel<false, true>), grid, dim3(NT), 0, st, d);
-    else hipLaunchKernelGGL((gemm_bx3_act_kernel<false, false>), grid, dim3(NT), 0, st, d);
+    // (<ADIR, BDIR> spelled 1 / 0: the recorded names have always carried them as numbers)
+    if (adir && bdir) VD_LAUNCH_OR_NAME(name, (gemm_bx3_act_kernel<1, 1>), grid, dim3(NT), 0, st, d);
+    else if (adir) VD_LAUNCH_OR_NAME(name, (gemm_bx3_act_kernel<1, 0>), grid, dim3(NT), 0, st, d);
+    else if (bdir) VD_LAUNCH_OR_NAME(name, (gemm_bx3_act_kernel<0, 1>), grid, dim3(NT), 0, st, d);
+    else VD_LAUNCH_OR_NAME(name, (gemm_bx3_act_kernel<0, 0>), grid, dim3(NT), 0, st, d);
 }
 
 static bool gemm_bx3_eligible(const vd_gemm_desc& d) {
@@ -920,33 +921,39 @@ static bool k32p_pick(const vd_gemm_desc& d) {
     return nt >= 192 && 4 * nt >= 3 * rounds * 256;
 }
 
+// vd_gemm_desc.pool2 (2x2 block sums in the epilogue): the flipped-tap 3x3 convolution on a packed operand with a bare epilogue, on the persistent kernel
+// (any image it takes) or at 16x16 / 32x32 outputs on a grid that no planner splits (>= 256 tiles of 128 x 128).  Asked by vd_gemm_tile before anything
+// else: a refused problem answers -1 there and VD_EINVAL at vd_gemm, before any launch.
+static bool pool2_ok(const vd_gemm_desc& d) {
+    if (!d.a_packed || d.b_mode != VD_B_CONV3_T || d.bias || d.rowadd || d.residual || d.accumulate) return false;
+    if (k32p_pick(d)) return true;
+    return d.OH == d.OW && (d.OW == 16 || d.OW == 32) && vd_cdiv(d.M, 128) * vd_cdiv(d.N, 128) >= 256;
+}
+
 // tile: vd_gemm_tile() of the problem -- 18 the persistent 16x16x32 kernel, 16 the 8x8 layers' 128 x 256 tiles with the channel loop split,
 // 15 / 12 the 128 x 512 / 128 x 256 tiles (eight waves, one workgroup per CU, unsplit), 8 the 128 x 128 tiles
-static int launch_bx3(const vd_gemm_desc& d, int tile, hipStream_t st) {
+static int launch_bx3(const vd_gemm_desc& d, int tile, hipStream_t st, char* name) {
     const int mode = d.b_mode == VD_B_CONV3 ? (d.gn_ss ? 3 : 0) : (d.b_mode == VD_B_CONV3_T ? 1 : (d.b_mode == VD_B_CONV3_S2 ? 4 : 2));
     if (tile == 18) {
-        if (d.pool2 && (mode != 1 || d.bias || d.rowadd || d.residual || d.accumulate)) {
-            vd_set_error("vd_gemm: pool2 needs VD_B_CONV3_T with a bare epilogue");
-            return VD_EINVAL;
+        if (vd_launch_conv3_k32p(d, mode, st, name) != 0) return VD_EINVAL;
+        if (name && d.OW > 32) {                                  // one instantiation walks 8 x 32 segments of any wider image: the image width beside it
+            char at[16];
+            snprintf(at, sizeof(at), "@%d", d.OW);
+            vd_name_append(name, at);
         }
-        return vd_launch_conv3_k32p(d, mode, st) == 0 ? 0 : VD_EINVAL;
+        return 0;
     }
     int splits, c_per;
     bx3_plan(d, splits, c_per);
-    if (splits > 1 && d.ws == nullptr) {
+    if (!name && splits > 1 && d.ws == nullptr) {
         vd_set_error("vd_gemm: split-K workspace required (%d splits): query vd_gemm_ws_floats()", splits);
-        return VD_EINVAL;
-    }
-    if (d.pool2 && (mode != 1 || splits != 1 || (d.OW != 16 && d.OW != 32) || d.bias || d.rowadd || d.residual || d.accumulate)) {
-        vd_set_error("vd_gemm: pool2 needs VD_B_CONV3_T with a_packed at 16x16 / 32x32 outputs on an unsplit grid (%d splits) and a bare epilogue",
-                     splits);
         return VD_EINVAL;
     }
     if (tile == 16) {
         dim3 grids(vd_cdiv(d.M, 128) * (d.N / 256), splits);
-        if (mode == 0) hipLaunchKernelGGL((conv3_bx3_kernel<8, 0, 2, 512, 2>), grids, dim3(512), 0, st, d, c_per);
-        else hipLaunchKernelGGL((conv3_bx3_kernel<8, 1, 2, 512, 2>), grids, dim3(512), 0, st, d, c_per);
-        if (splits > 1) launch_splitk_epilogue(d, splits, st);
+        if (mode == 0) VD_LAUNCH_OR_NAME(name, (conv3_bx3_kernel<8, 0, 2, 512, 2>), grids, dim3(512), 0, st, d, c_per);
+        else VD_LAUNCH_OR_NAME(name, (conv3_bx3_kernel<8, 1, 2, 512, 2>), grids, dim3(512), 0, st, d, c_per);
+        if (!name && splits > 1) launch_splitk_epilogue(d, splits, st);
         return 0;
     }
     // 128 x 256 / 128 x 512 tiles where whole rounds of 256 workgroups come out (bx3_big_tile): the weight operand is then fetched from L2 and
@@ -955,10 +962,10 @@ static int launch_bx3(const vd_gemm_desc& d, int tile, hipStream_t st) {
     if (tile == 15) {
         dim3 gridh(vd_cdiv(d.M, 128) * (d.N / 512), 1);
         switch (mode) {
-        case 0: hipLaunchKernelGGL((conv3_bx3_kernel<32, 0, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
-        case 1: hipLaunchKernelGGL((conv3_bx3_kernel<32, 1, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
-        case 2: hipLaunchKernelGGL((conv3_bx3_kernel<32, 2, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
-        default: hipLaunchKernelGGL((conv3_bx3_kernel<32, 3, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
+        case 0: VD_LAUNCH_OR_NAME(name, (conv3_bx3_kernel<32, 0, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
+        case 1: VD_LAUNCH_OR_NAME(name, (conv3_bx3_kernel<32, 1, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
+        case 2: VD_LAUNCH_OR_NAME(name, (conv3_bx3_kernel<32, 2, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
+        default: VD_LAUNCH_OR_NAME(name, (conv3_bx3_kernel<32, 3, 4, 512, 2>), gridh, dim3(512), 0, st, d, c_per); break;
         }
         return 0;
     }
@@ -967,7 +974,7 @@ static int launch_bx3(const vd_gemm_desc& d, int tile, hipStream_t st) {
         dim3 gridb(vd_cdiv(d.M, 128) * (d.N / 256), 1);
 #define BX3_BIG(WW, MD)                                                                                   \
     if (!done && d.OW == WW && mode == MD) {                                                              \
-        hipLaunchKernelGGL((conv3_bx3_kernel<WW, MD, 2, 512, 2>), gridb, dim3(512), 0, st, d, c_per);      \
+        VD_LAUNCH_OR_NAME(name, (conv3_bx3_kernel<WW, MD, 2, 512, 2>), gridb, dim3(512), 0, st, d, c_per); \
         done = true;                                                                                      \
     }
         BX3_BIG(32, 0) BX3_BIG(32, 1) BX3_BIG(32, 2) BX3_BIG(32, 3)
@@ -976,9 +983,10 @@ static int launch_bx3(const vd_gemm_desc& d, int tile, hipStream_t st) {
         return done ? 0 : VD_EINVAL;
     }
     dim3 grid(vd_cdiv(d.M, 128) * vd_cdiv(d.N, 128), splits);
+    const int tw = d.OW >= 128 && d.OW % 128 == 0 ? 128 : d.OW;      // tile width: the image's, or 128-pixel row segments of wider ones
 #define BX3_CASE(WW, MD)                                                                      \
-    if (!done && d.OW == WW && mode == MD) {                                                  \
-        hipLaunchKernelGGL((conv3_bx3_kernel<WW, MD, 2>), grid, dim3(NT), 0, st, d, c_per);   \
+    if (!done && tw == WW && mode == MD) {                                                    \
+        VD_LAUNCH_OR_NAME(name, (conv3_bx3_kernel<WW, MD, 2, 256, 2>), grid, dim3(NT), 0, st, d, c_per); \
         done = true;                                                                          \
     }
     BX3_CASE(32, 0) BX3_CASE(32, 1) BX3_CASE(32, 2) BX3_CASE(32, 3)
@@ -986,17 +994,11 @@ static int launch_bx3(const vd_gemm_desc& d, int tile, hipStream_t st) {
     BX3_CASE(8, 0) BX3_CASE(8, 1) BX3_CASE(8, 2)
     BX3_CASE(4, 0) BX3_CASE(4, 1)
     BX3_CASE(32, 4) BX3_CASE(16, 4) BX3_CASE(8, 4) BX3_CASE(4, 4)
-#define BX3_WIDE(WW, MD)                                                                      \
-    if (!done && (WW == 64 ? d.OW == 64 : (d.OW >= 128 && d.OW % 128 == 0)) && mode == MD) {  \
-        hipLaunchKernelGGL((conv3_bx3_kernel<WW, MD, 2>), grid, dim3(NT), 0, st, d, c_per);   \
-        done = true;                                                                          \
-    }
-    BX3_WIDE(64, 0) BX3_WIDE(64, 1) BX3_WIDE(64, 2)
-    BX3_WIDE(128, 0) BX3_WIDE(128, 1) BX3_WIDE(128, 2)
-    BX3_WIDE(64, 4) BX3_WIDE(128, 4)
-#undef BX3_WIDE
+    BX3_CASE(64, 0) BX3_CASE(64, 1) BX3_CASE(64, 2)
+    BX3_CASE(128, 0) BX3_CASE(128, 1) BX3_CASE(128, 2)
+    BX3_CASE(64, 4) BX3_CASE(128, 4)
 #undef BX3_CASE
     if (!done) return VD_EINVAL;
-    if (splits > 1) launch_splitk_epilogue(d, splits, st);
+    if (!name && splits > 1) launch_splitk_epilogue(d, splits, st);
     return 0;
 }

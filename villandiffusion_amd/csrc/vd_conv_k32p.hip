@@ -705,9 +705,9 @@ bool vd_conv3_k32p_eligible(const vd_gemm_desc& d) {
     return true;
 }
 
-int vd_launch_conv3_k32p(const vd_gemm_desc& d, int mode, hipStream_t st) {
+int vd_launch_conv3_k32p(const vd_gemm_desc& d, int mode, hipStream_t st, char* name) {
     static int n_cu = 0;
-    if (n_cu == 0) {
+    if (!name && n_cu == 0) {
         int dev = 0;
         hipDeviceProp_t p;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return -1;
@@ -743,25 +743,25 @@ int vd_launch_conv3_k32p(const vd_gemm_desc& d, int mode, hipStream_t st) {
 #ifdef VD_K32P_VARIANTS
 #define VD_K32P_CASE(WW, MD)                                                                                         \
     if (TW == WW && mode == MD) {                                                                                    \
-        if (dma && pipe) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false>), dim3(grid), dim3(512), 0, st, a);        \
-        else if (dma) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, false, false>), dim3(grid), dim3(512), 0, st, a);          \
-        else if (pipe) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, false, true, false>), dim3(grid), dim3(512), 0, st, a);         \
-        else hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, false, false, false>), dim3(grid), dim3(512), 0, st, a);                  \
+        if (dma && pipe) VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, true, true, false>), dim3(grid), dim3(512), 0, st, a);        \
+        else if (dma) VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, true, false, false>), dim3(grid), dim3(512), 0, st, a);          \
+        else if (pipe) VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, false, true, false>), dim3(grid), dim3(512), 0, st, a);         \
+        else VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, false, false, false>), dim3(grid), dim3(512), 0, st, a);                  \
         return 0;                                                                                                    \
     }
 #else
 #define VD_K32P_CASE(WW, MD)                                                                                         \
     if (TW == WW && mode == MD) {                                                                                    \
-        if (d.math == 2) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, true>), dim3(grid), dim3(512), 0, st, a);   \
-        else if (d.math == 3) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false, false, true>), dim3(grid), dim3(512), 0, st, a); \
-        else hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false>), dim3(grid), dim3(512), 0, st, a);    \
+        if (d.math == 2) VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, true, true, true, false>), dim3(grid), dim3(512), 0, st, a);   \
+        else if (d.math == 3) VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, true, true, false, false, true>), dim3(grid), dim3(512), 0, st, a); \
+        else VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, true, true, false, false>), dim3(grid), dim3(512), 0, st, a); \
         return 0;                                                                                                    \
     }
 #endif
 #define VD_K32P_PS(WW, MD)                                                                                           \
     if (d.b_presplit && TW == WW && mode == MD) {                                                                    \
-        if (d.math == 3) hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false, true, true>), dim3(grid), dim3(512), 0, st, a); \
-        else hipLaunchKernelGGL((conv3_k32p_kernel<WW, MD, true, true, false, true>), dim3(grid), dim3(512), 0, st, a); \
+        if (d.math == 3) VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, true, true, false, true, true>), dim3(grid), dim3(512), 0, st, a); \
+        else VD_LAUNCH_OR_NAME(name, (conv3_k32p_kernel<WW, MD, true, true, false, true>), dim3(grid), dim3(512), 0, st, a); \
         return 0;                                                                                                    \
     }
     VD_K32P_PS(32, 0) VD_K32P_PS(32, 1) VD_K32P_PS(32, 2) VD_K32P_PS(16, 0) VD_K32P_PS(16, 1) VD_K32P_PS(16, 2)

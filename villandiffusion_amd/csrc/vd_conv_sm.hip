@@ -327,7 +327,7 @@ bool vd_conv3_sm_eligible(const vd_gemm_desc& d) {
     return vd_cdiv(d.M, 64) * vd_cdiv(nb, imgs) >= (d.OW == 8 ? 64 : 256);
 }
 
-int vd_launch_conv3_sm(const vd_gemm_desc& d, hipStream_t st) {
+int vd_launch_conv3_sm(const vd_gemm_desc& d, hipStream_t st, char* name) {
     sm_args a;
     a.d = d;
 #ifdef VD_SM_STAMPS
@@ -342,8 +342,8 @@ int vd_launch_conv3_sm(const vd_gemm_desc& d, hipStream_t st) {
     // profiles/r06_conv_sm_ab.txt)
 #define VD_SM_CASE(WW, MD, IM)                                                                                   \
     if (d.OW == WW && mode == MD && imgs == IM) {                                                                \
-        if (d.math == 3) hipLaunchKernelGGL((conv3_sm_kernel<WW, MD, IM, 1, true>), dim3(a.n_tiles), dim3(256), 0, st, a); \
-        else hipLaunchKernelGGL((conv3_sm_kernel<WW, MD, IM, 1>), dim3(a.n_tiles), dim3(256), 0, st, a);     \
+        if (d.math == 3) VD_LAUNCH_OR_NAME(name, (conv3_sm_kernel<WW, MD, IM, 1, true>), dim3(a.n_tiles), dim3(256), 0, st, a); \
+        else VD_LAUNCH_OR_NAME(name, (conv3_sm_kernel<WW, MD, IM, 1>), dim3(a.n_tiles), dim3(256), 0, st, a);     \
         return 0;                                                                                                \
     }
     VD_SM_CASE(8, 0, 2) VD_SM_CASE(8, 1, 2) VD_SM_CASE(4, 0, 4) VD_SM_CASE(4, 1, 4)

@@ -17,16 +17,17 @@
 #include <stdlib.h>
 
 // vd_conv_k32p.hip: the persistent 16x16x32 split-precision 3x3 convolution (its own translation unit)
+// (the launchers below: `name` as VD_LAUNCH_OR_NAME -- not NULL: write the instantiation, launch nothing, touch no device)
 bool vd_conv3_k32p_eligible(const vd_gemm_desc& d);
-int vd_launch_conv3_k32p(const vd_gemm_desc& d, int mode, hipStream_t st);
+int vd_launch_conv3_k32p(const vd_gemm_desc& d, int mode, hipStream_t st, char* name);
 // vd_presplit.hip: the grouped 3x3 weight gradient with both operands pre-split (LDS-DMA + transposed reads)
-int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks, hipStream_t st, bool one);
+int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks, hipStream_t st, bool one, char* name);
 // vd_conv_sm.hip: the whole-K 16x16x32 split-precision 3x3 convolution of the 8x8 / 4x4 levels (round 6)
 bool vd_conv3_sm_eligible(const vd_gemm_desc& d);
-int vd_launch_conv3_sm(const vd_gemm_desc& d, hipStream_t st);
+int vd_launch_conv3_sm(const vd_gemm_desc& d, hipStream_t st, char* name);
 // vd_gemm_k32p.hip: the persistent 16x16x32 split-precision 1x1 convolution / plain product
 bool vd_gemm1x1_k32p_pick(const vd_gemm_desc& d);
-int vd_launch_gemm1x1_k32p(const vd_gemm_desc& d, hipStream_t st);
+int vd_launch_gemm1x1_k32p(const vd_gemm_desc& d, hipStream_t st, char* name);
 
 namespace {
 
@@ -775,38 +776,33 @@ static bool patch_wide(const vd_gemm_desc& d) {
     return wgs >= 512 && wgs % 512 == 0;
 }
 
-static int launch_patch(const vd_gemm_desc& d, hipStream_t st) {
+static int launch_patch(const vd_gemm_desc& d, hipStream_t st, char* name) {
     int splits, ks_per;
     patch_plan(d, splits, ks_per);
     const int mode_ = d.b_mode == VD_B_CONV3 ? (d.gn_ss ? 3 : 0) : (d.b_mode == VD_B_CONV3_T ? 1 : (d.b_mode == VD_B_CONV3_S2 ? 4 : 2));
     if (splits == 1 && patch_wide(d)) {
         dim3 grid(vd_cdiv(d.M, 128) * (d.N / 256), 1);
-        if (mode_ == 0) hipLaunchKernelGGL((conv3_patch_kernel<32, 0, 4>), grid, dim3(NT), 0, st, d, ks_per);
-        else if (mode_ == 3) hipLaunchKernelGGL((conv3_patch_kernel<32, 3, 4>), grid, dim3(NT), 0, st, d, ks_per);
-        else if (mode_ == 1) hipLaunchKernelGGL((conv3_patch_kernel<32, 1, 4>), grid, dim3(NT), 0, st, d, ks_per);
-        else hipLaunchKernelGGL((conv3_patch_kernel<32, 2, 4>), grid, dim3(NT), 0, st, d, ks_per);
+        if (mode_ == 0) VD_LAUNCH_OR_NAME(name, (conv3_patch_kernel<32, 0, 4>), grid, dim3(NT), 0, st, d, ks_per);
+        else if (mode_ == 3) VD_LAUNCH_OR_NAME(name, (conv3_patch_kernel<32, 3, 4>), grid, dim3(NT), 0, st, d, ks_per);
+        else if (mode_ == 1) VD_LAUNCH_OR_NAME(name, (conv3_patch_kernel<32, 1, 4>), grid, dim3(NT), 0, st, d, ks_per);
+        else VD_LAUNCH_OR_NAME(name, (conv3_patch_kernel<32, 2, 4>), grid, dim3(NT), 0, st, d, ks_per);
         return 0;
     }
-    if (splits > 1 && d.ws == nullptr) {
+    if (!name && splits > 1 && d.ws == nullptr) {
         vd_set_error("vd_gemm: split-K workspace required (%d splits): query vd_gemm_ws_floats()", splits);
         return VD_EINVAL;
     }
     dim3 grid(vd_cdiv(d.M, 128) * vd_cdiv(d.N, 128), splits);
     const int mode = mode_;
     bool done = false;
+    const int tw = d.OW >= 128 && d.OW % 128 == 0 ? 128 : d.OW;      // tile width: the image's, or 128-pixel row segments of wider ones
 #define VD_PATCH_CASE(WW, MD)                                                                            \
-    if (!done && d.OW == WW && mode == MD) {                                                             \
-        hipLaunchKernelGGL((conv3_patch_kernel<WW, MD, 2>), grid, dim3(NT), 0, st, d, ks_per);              \
+    if (!done && tw == WW && mode == MD) {                                                               \
+        VD_LAUNCH_OR_NAME(name, (conv3_patch_kernel<WW, MD, 2>), grid, dim3(NT), 0, st, d, ks_per);        \
         done = true;                                                                                     \
     }
-#define VD_PATCH_WIDE(WW, MD)                                                                            \
-    if (!done && (WW == 64 ? d.OW == 64 : (d.OW >= 128 && d.OW % 128 == 0)) && mode == MD) {             \
-        hipLaunchKernelGGL((conv3_patch_kernel<WW, MD, 2>), grid, dim3(NT), 0, st, d, ks_per);              \
-        done = true;                                                                                     \
-    }
-    VD_PATCH_WIDE(64, 0) VD_PATCH_WIDE(64, 1) VD_PATCH_WIDE(64, 2)
-    VD_PATCH_WIDE(128, 0) VD_PATCH_WIDE(128, 1) VD_PATCH_WIDE(128, 2)
-#undef VD_PATCH_WIDE
+    VD_PATCH_CASE(64, 0) VD_PATCH_CASE(64, 1) VD_PATCH_CASE(64, 2)
+    VD_PATCH_CASE(128, 0) VD_PATCH_CASE(128, 1) VD_PATCH_CASE(128, 2)
     VD_PATCH_CASE(32, 0) VD_PATCH_CASE(32, 1) VD_PATCH_CASE(32, 2) VD_PATCH_CASE(32, 3)
     VD_PATCH_CASE(16, 0) VD_PATCH_CASE(16, 1) VD_PATCH_CASE(16, 2) VD_PATCH_CASE(16, 3)
     VD_PATCH_CASE(8, 0) VD_PATCH_CASE(8, 1) VD_PATCH_CASE(8, 2)
@@ -814,7 +810,7 @@ static int launch_patch(const vd_gemm_desc& d, hipStream_t st) {
     VD_PATCH_CASE(16, 4) VD_PATCH_CASE(8, 4) VD_PATCH_CASE(4, 4)
 #undef VD_PATCH_CASE
     if (!done) return VD_EINVAL;
-    if (splits > 1) launch_splitk_epilogue(d, splits, st);
+    if (!name && splits > 1) launch_splitk_epilogue(d, splits, st);
     return 0;
 }
 
@@ -1014,26 +1010,26 @@ static bool smallm_eligible(const vd_gemm_desc& d) {
     return d.W == 16 && d.H % 16 == 0;
 }
 
-static int launch_smallm(const vd_gemm_desc& d, hipStream_t st) {
+static int launch_smallm(const vd_gemm_desc& d, hipStream_t st, char* name) {
     const int nb = d.N / d.NP;
     if (d.b_mode == VD_B_CONV3_T) {
         const int64_t quads = (int64_t)nb * d.H * (d.W / 4);
-        hipLaunchKernelGGL((conv3_fewout_kernel<4, 8, true>), dim3((unsigned)((quads + 63) / 64)), dim3(512), 0, st, d, quads);
+        VD_LAUNCH_OR_NAME(name, (conv3_fewout_kernel<4, 8, true>), dim3((unsigned)((quads + 63) / 64)), dim3(512), 0, st, d, quads);
         return 0;
     }
     if (fewout_eligible(d)) {
         const int64_t quads = (int64_t)nb * d.H * (d.W / 4);
         // eight waves per 256 pixels (round 6; four until then): 31 against 48 us for conv_out at B = 128 -- the loop is a latency chain (loads -> 100 FMAs per
         // channel) and four waves per workgroup left two per SIMD; sixteen: 34 us
-        hipLaunchKernelGGL((conv3_fewout_kernel<4, 8>), dim3((unsigned)((quads + 63) / 64)), dim3(512), 0, st, d, quads);
+        VD_LAUNCH_OR_NAME(name, (conv3_fewout_kernel<4, 8, false>), dim3((unsigned)((quads + 63) / 64)), dim3(512), 0, st, d, quads);
         return 0;
     }
     if (d.W % 32 == 0) {
         dim3 grid((unsigned)(nb * (d.H / 8) * (d.W / 32)));
-        hipLaunchKernelGGL((conv3_smallm_kernel<32, 4>), grid, dim3(256), 0, st, d);
+        VD_LAUNCH_OR_NAME(name, (conv3_smallm_kernel<32, 4>), grid, dim3(256), 0, st, d);
     } else {
         dim3 grid((unsigned)(nb * (d.H / 16)));
-        hipLaunchKernelGGL((conv3_smallm_kernel<16, 4>), grid, dim3(256), 0, st, d);
+        VD_LAUNCH_OR_NAME(name, (conv3_smallm_kernel<16, 4>), grid, dim3(256), 0, st, d);
     }
     return 0;
 }
@@ -2096,12 +2092,14 @@ __global__ __launch_bounds__(256) void colsum_seg_kernel(const int64_t* __restri
 }
 
 template <int WM, int WN>
-int launch_gemm_t(const vd_gemm_desc& d, hipStream_t st) {
+int launch_gemm_t(const vd_gemm_desc& d, hipStream_t st, char* name) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     const int grid = vd_cdiv(d.M, BM) * vd_cdiv(d.N, BN);
+    // (recorded by tile size and enumerator, "gemm_kernel<128x128,ROW,CONV3_S2>": the enumerators' text less its VD_A_ / VD_B_ prefix)
 #define VD_GEMM_CASE(AM, BMD)                                                                   \
     if (d.a_mode == AM && d.b_mode == BMD) {                                                    \
-        hipLaunchKernelGGL((gemm_kernel<WM, WN, AM, BMD>), dim3(grid), dim3(NT), 0, st, d);     \
+        if (name) snprintf(name, VD_NAME_LEN, "gemm_kernel<%dx%d,%s,%s>", BM, BN, &#AM[5], &#BMD[5]); \
+        else hipLaunchKernelGGL((gemm_kernel<WM, WN, AM, BMD>), dim3(grid), dim3(NT), 0, st, d); \
         return 0;                                                                               \
     }
     VD_GEMM_CASE(VD_A_ROW, VD_B_PLAIN)
@@ -2129,12 +2127,13 @@ int pick_tile(int M, int N, int max_bn) {
 }
 
 template <int WM, int WN>
-int launch_wgrad_t(const vd_wgrad_desc& d, int splits, int kk_per, hipStream_t st) {
+int launch_wgrad_t(const vd_wgrad_desc& d, int splits, int kk_per, hipStream_t st, char* name) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     dim3 grid(vd_cdiv(d.M, BM) * vd_cdiv(d.C * d.T, BN), splits);
 #define VD_WG_CASE(BMD)                                                                          \
     if (d.mode == BMD) {                                                                         \
-        hipLaunchKernelGGL((wgrad_kernel<WM, WN, BMD>), grid, dim3(NT), 0, st, d, kk_per);       \
+        if (name) snprintf(name, VD_NAME_LEN, "wgrad_kernel<%dx%d,%s>", BM, BN, &#BMD[5]);       \
+        else hipLaunchKernelGGL((wgrad_kernel<WM, WN, BMD>), grid, dim3(NT), 0, st, d, kk_per);  \
         return 0;                                                                                \
     }
     VD_WG_CASE(VD_B_PLAIN)
@@ -2172,6 +2171,7 @@ extern "C" int64_t vd_gemm_ws_floats(const vd_gemm_desc* desc) {
 extern "C" int vd_gemm_tile(const vd_gemm_desc* desc) {
     if (!desc) return 0;
     const vd_gemm_desc& d = *desc;
+    if (d.pool2 && !pool2_ok(d)) return -1;
     if (d.a_packed && d.math == 2) {      // opt-in f16 operands (vd_conv3_pack_weights_f16_multi): only the persistent 16x16x32 kernels read them
         if (bx3_eligible(d) && !bx3_big_split(d) && k32p_pick(d)) return 18;
         if (gemm_bx3_eligible(d) && vd_gemm1x1_k32p_pick(d)) return 19;
@@ -2217,7 +2217,9 @@ extern "C" int vd_gemm_tile(const vd_gemm_desc* desc) {
     return tile;
 }
 
-extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
+// vd_gemm (name == NULL) and vd_gemm_kernel_name (name: char[VD_NAME_LEN]) are ONE walk through the checks and the launch switch; with a name the
+// branch that would launch writes its instantiation instead, nothing below touches the device or asks for the workspace, and the tile is returned.
+static int gemm_run(const vd_gemm_desc* desc, hipStream_t st, char* name) {
     VD_REQUIRE(desc != nullptr, "vd_gemm: null desc");
     vd_gemm_desc d = *desc;
     VD_REQUIRE(d.A && d.B && d.D, "vd_gemm: null operand");
@@ -2247,7 +2249,8 @@ extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
     VD_REQUIRE(tile != -1, "vd_gemm: a_packed (split-precision bf16) needs a 3x3 convolution with 8x8 / 16x16 / 32x32 outputs, "
                            "C %% 16 == 0, M >= 64, or a VD_B_PLAIN product with shared A, NP %% 128 == 0, K %% 16 == 0, M >= 64; "
                            "a_packed_mpad = M rounded up to 128; math = 1 needs per-batch A, PLAIN / KCONTIG B, NP %% 128 == 0, K %% 16 == 0, K >= 32, M >= 64; "
-                           "math = 2 / 3 need the persistent 16x16x32 kernels (vd_gemm_tile 18 / 19; math = 3 also 20)");
+                           "math = 2 / 3 need the persistent 16x16x32 kernels (vd_gemm_tile 18 / 19; math = 3 also 20); "
+                           "pool2 needs VD_B_CONV3_T with a_packed and a bare epilogue, on the persistent kernel or at 16x16 / 32x32 outputs with >= 256 tiles of 128 x 128");
     VD_REQUIRE(d.b_presplit == 0 || (d.b_presplit == 1 && tile == 18),
                "vd_gemm: a pre-split B operand (b_presplit = %d) is read by the persistent 16x16x32 convolution only (vd_gemm_tile() == 18; this problem: %d)",
                d.b_presplit, tile);
@@ -2257,50 +2260,53 @@ extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) {
     VD_REQUIRE(!d.act_out || (tile == 18 && d.gn_ss), "vd_gemm: act_out is written by the persistent 16x16x32 3x3 convolution with gn_ss only (vd_gemm_tile() == 18)");
     VD_REQUIRE(!d.gn_part || (tile == 18 && !d.pool2),
                "vd_gemm: gn_part is written by the persistent 16x16x32 split-precision 3x3 kernel only (vd_gemm_tile() == 18)");
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
+    int rc = 0;
     switch (tile) {
-        case 1: rc = launch_gemm_t<2, 2>(d, st); break;
-        case 2: rc = launch_gemm_t<1, 2>(d, st); break;
-        case 3: rc = launch_gemm_t<1, 1>(d, st); break;
+        case 1: rc = launch_gemm_t<2, 2>(d, st, name); break;
+        case 2: rc = launch_gemm_t<1, 2>(d, st, name); break;
+        case 3: rc = launch_gemm_t<1, 1>(d, st, name); break;
         case 4:
-        case 6: rc = launch_patch(d, st); break;
-        case 7: rc = launch_smallm(d, st); break;
-        case 8: case 12: case 15: case 16: case 18: rc = launch_bx3(d, tile, st); break;
-        case 19: rc = vd_launch_gemm1x1_k32p(d, st) == 0 ? 0 : VD_EINVAL; break;
-        case 20: rc = vd_launch_conv3_sm(d, st) == 0 ? 0 : VD_EINVAL; break;
-        case 10: launch_gemm_bx3_act(d, st); rc = 0; break;
-        case 13:
-            hipLaunchKernelGGL(gemm_bx3_kernel<512>, dim3(vd_cdiv(d.M, 128) * (d.N / 256)), dim3(512), 0, st, d, 1 << 30);
-            rc = 0;
-            break;
+        case 6: rc = launch_patch(d, st, name); break;
+        case 7: rc = launch_smallm(d, st, name); break;
+        case 8: case 12: case 15: case 16: case 18: rc = launch_bx3(d, tile, st, name); break;
+        case 19: rc = vd_launch_gemm1x1_k32p(d, st, name) == 0 ? 0 : VD_EINVAL; break;
+        case 20: rc = vd_launch_conv3_sm(d, st, name) == 0 ? 0 : VD_EINVAL; break;
+        case 10: launch_gemm_bx3_act(d, st, name); break;
+        case 13: VD_LAUNCH_OR_NAME(name, gemm_bx3_kernel<512>, dim3(vd_cdiv(d.M, 128) * (d.N / 256)), dim3(512), 0, st, d, 1 << 30); break;
         case 9: {
             int splits, st_per;
             gemm_bx3_plan(d, splits, st_per);
-            VD_REQUIRE(splits == 1 || d.ws, "vd_gemm: split-K 1x1 launch needs the workspace (vd_gemm_ws_floats)");
-            hipLaunchKernelGGL(gemm_bx3_kernel<256>, dim3(vd_cdiv(d.M, 128) * (d.N / 128), splits), dim3(NT), 0, st, d, st_per);
-            if (splits > 1) launch_splitk_epilogue(d, splits, st);
-            rc = 0;
+            VD_REQUIRE(name || splits == 1 || d.ws, "vd_gemm: split-K 1x1 launch needs the workspace (vd_gemm_ws_floats)");
+            VD_LAUNCH_OR_NAME(name, gemm_bx3_kernel<256>, dim3(vd_cdiv(d.M, 128) * (d.N / 128), splits), dim3(NT), 0, st, d, st_per);
+            if (!name && splits > 1) launch_splitk_epilogue(d, splits, st);
             break;
         }
-        case 11:
-            hipLaunchKernelGGL(gemm_bx3_persist_kernel, dim3(512), dim3(NT), 0, st, d, vd_cdiv(d.M, 128) * (d.N / 128));
-            rc = 0;
-            break;
+        case 11: VD_LAUNCH_OR_NAME(name, gemm_bx3_persist_kernel, dim3(512), dim3(NT), 0, st, d, vd_cdiv(d.M, 128) * (d.N / 128)); break;
         case 5: {
             const int grid = vd_cdiv(d.M, 128) * (d.N / 128);
-            if (d.a_mode == VD_A_ROW)
-                hipLaunchKernelGGL((gemm_plain_kernel<VD_A_ROW>), dim3(grid), dim3(NT), 0, st, d);
-            else
-                hipLaunchKernelGGL((gemm_plain_kernel<VD_A_COL>), dim3(grid), dim3(NT), 0, st, d);
-            rc = 0;
+            if (d.a_mode == VD_A_ROW) VD_LAUNCH_OR_NAME(name, gemm_plain_kernel<0>, dim3(grid), dim3(NT), 0, st, d);       // <VD_A_ROW>
+            else VD_LAUNCH_OR_NAME(name, gemm_plain_kernel<1>, dim3(grid), dim3(NT), 0, st, d);                           // <VD_A_COL>
             break;
         }
         default: vd_set_error("vd_gemm: bad tile %d", tile); return VD_EINVAL;
     }
-    if (rc) return rc;
+    if (rc || name) return rc ? rc : tile;
     VD_LAUNCH_CHECK("vd_gemm");
     return 0;
+}
+
+extern "C" int vd_gemm(const vd_gemm_desc* desc, void* stream) { return gemm_run(desc, (hipStream_t)stream, nullptr); }
+
+// rc of a name walk (< 0: refused) and its name -> the caller's buffer: the whole name, or an empty one with VD_EINVAL
+static int name_out(int rc, const char* buf, char* name, int name_len) {
+    if (!name || name_len <= 0) return VD_EINVAL;
+    snprintf(name, name_len, "%s", rc < 0 ? "" : buf);
+    return rc < 0 ? VD_EINVAL : rc;
+}
+
+extern "C" int vd_gemm_kernel_name(const vd_gemm_desc* desc, char* name, int name_len) {
+    char buf[VD_NAME_LEN] = "";
+    return name_out(gemm_run(desc, nullptr, buf), buf, name, name_len);
 }
 
 extern "C" int64_t vd_conv3_packed_bytes(int M, int C, int taps) {
@@ -2375,7 +2381,8 @@ extern "C" int vd_conv_wgrad_plan(const vd_wgrad_desc* desc, int* tile, int* spl
     return 0;
 }
 
-extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) {
+// vd_conv_wgrad (name == NULL) and vd_conv_wgrad_kernel_name: one walk, as gemm_run
+static int wgrad_run(const vd_wgrad_desc* desc, hipStream_t st, char* name) {
     VD_REQUIRE(desc != nullptr, "vd_conv_wgrad: null desc");
     vd_wgrad_desc d = *desc;
     VD_REQUIRE(d.dY && d.X && d.dW, "vd_conv_wgrad: null operand");
@@ -2394,74 +2401,55 @@ extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) {
     const int Ncols = d.C * d.T;
     int tile, splits, kk_per;
     wgrad_plan(d, tile, splits, kk_per);
-    VD_REQUIRE(splits == 1 || d.ws != nullptr, "vd_conv_wgrad: workspace required for %d splits", splits);
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
+    VD_REQUIRE(name || splits == 1 || d.ws != nullptr, "vd_conv_wgrad: workspace required for %d splits", splits);
+    int rc = 0;
     switch (tile) {
         case 4: {
             dim3 grid(vd_cdiv(d.M, 128) * vd_cdiv(d.C, 64) * 3, splits);
-            rc = 0;
             if (wgrad_patch_kind(d) == 4) {
                 const bool up = d.mode == VD_B_CONV3_UP;
-#define VD_WK32(WW)                                                                                     \
-    do {                                                                                                \
-        if (up) hipLaunchKernelGGL((wgrad_k32_kernel<WW, 2>), grid, dim3(NT), 0, st, d, kk_per);        \
-        else hipLaunchKernelGGL((wgrad_k32_kernel<WW, 0>), grid, dim3(NT), 0, st, d, kk_per);           \
-    } while (0)
                 if (d.mode == VD_B_CONV3_S2) {
-                    if (d.OW >= 64) hipLaunchKernelGGL((wgrad_bx3_kernel<32, 4, true>), grid, dim3(NT), 0, st, d, kk_per);
-                    else if (d.OW == 32) hipLaunchKernelGGL((wgrad_bx3_kernel<32, 4>), grid, dim3(NT), 0, st, d, kk_per);
-                    else if (d.OW == 16) hipLaunchKernelGGL((wgrad_bx3_kernel<16, 4>), grid, dim3(NT), 0, st, d, kk_per);
-                    else hipLaunchKernelGGL((wgrad_bx3_kernel<8, 4>), grid, dim3(NT), 0, st, d, kk_per);
-                } else if (d.OW >= 64 && up) hipLaunchKernelGGL((wgrad_bx3_kernel<32, 2, true>), grid, dim3(NT), 0, st, d, kk_per);
-                else if (d.OW >= 64) hipLaunchKernelGGL((wgrad_bx3_kernel<32, 0, true>), grid, dim3(NT), 0, st, d, kk_per);
-                else if (d.OW == 4) hipLaunchKernelGGL((wgrad_bx3_kernel<4, 0>), grid, dim3(NT), 0, st, d, kk_per);
-                else if (d.OW == 32) VD_WK32(32);
-                else if (d.OW == 16) VD_WK32(16);
-                else VD_WK32(8);
-#undef VD_WK32
+                    if (d.OW >= 64) VD_LAUNCH_OR_NAME(name, (wgrad_bx3_kernel<32, 4, true>), grid, dim3(NT), 0, st, d, kk_per);
+                    else if (d.OW == 32) VD_LAUNCH_OR_NAME(name, (wgrad_bx3_kernel<32, 4>), grid, dim3(NT), 0, st, d, kk_per);
+                    else if (d.OW == 16) VD_LAUNCH_OR_NAME(name, (wgrad_bx3_kernel<16, 4>), grid, dim3(NT), 0, st, d, kk_per);
+                    else VD_LAUNCH_OR_NAME(name, (wgrad_bx3_kernel<8, 4>), grid, dim3(NT), 0, st, d, kk_per);
+                } else if (d.OW >= 64 && up) VD_LAUNCH_OR_NAME(name, (wgrad_bx3_kernel<32, 2, true>), grid, dim3(NT), 0, st, d, kk_per);
+                else if (d.OW >= 64) VD_LAUNCH_OR_NAME(name, (wgrad_bx3_kernel<32, 0, true>), grid, dim3(NT), 0, st, d, kk_per);
+                else if (d.OW == 4) VD_LAUNCH_OR_NAME(name, (wgrad_bx3_kernel<4, 0>), grid, dim3(NT), 0, st, d, kk_per);
+                else if (d.OW == 32 && up) VD_LAUNCH_OR_NAME(name, (wgrad_k32_kernel<32, 2>), grid, dim3(NT), 0, st, d, kk_per);
+                else if (d.OW == 32) VD_LAUNCH_OR_NAME(name, (wgrad_k32_kernel<32, 0>), grid, dim3(NT), 0, st, d, kk_per);
+                else if (d.OW == 16 && up) VD_LAUNCH_OR_NAME(name, (wgrad_k32_kernel<16, 2>), grid, dim3(NT), 0, st, d, kk_per);
+                else if (d.OW == 16) VD_LAUNCH_OR_NAME(name, (wgrad_k32_kernel<16, 0>), grid, dim3(NT), 0, st, d, kk_per);
+                else if (up) VD_LAUNCH_OR_NAME(name, (wgrad_k32_kernel<8, 2>), grid, dim3(NT), 0, st, d, kk_per);
+                else VD_LAUNCH_OR_NAME(name, (wgrad_k32_kernel<8, 0>), grid, dim3(NT), 0, st, d, kk_per);
             } else if (wgrad_patch_kind(d) == 3) {
                 const int ohs = ilog2_exact(d.OH);
                 const bool up = d.mode == VD_B_CONV3_UP;
-                if (d.OW == 32) {
-                    if (up) hipLaunchKernelGGL((wgrad_patch_gen_kernel<2, 2, 64>), grid, dim3(NT), 0, st, d, kk_per, ohs, 0);
-                    else hipLaunchKernelGGL((wgrad_patch_gen_kernel<2, 0, 64>), grid, dim3(NT), 0, st, d, kk_per, ohs, 0);
-                } else {
-                    if (up) hipLaunchKernelGGL((wgrad_patch_gen_kernel<4, 2, 64>), grid, dim3(NT), 0, st, d, kk_per, ohs, 0);
-                    else hipLaunchKernelGGL((wgrad_patch_gen_kernel<4, 0, 64>), grid, dim3(NT), 0, st, d, kk_per, ohs, 0);
-                }
+                if (d.OW == 32 && up) VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<2, 2, 64>), grid, dim3(NT), 0, st, d, kk_per, ohs, 0);
+                else if (d.OW == 32) VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<2, 0, 64>), grid, dim3(NT), 0, st, d, kk_per, ohs, 0);
+                else if (up) VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<4, 2, 64>), grid, dim3(NT), 0, st, d, kk_per, ohs, 0);
+                else VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<4, 0, 64>), grid, dim3(NT), 0, st, d, kk_per, ohs, 0);
             } else if (wgrad_patch_kind(d) == 2) {
                 const int ohs = ilog2_exact(d.OH), sgs = d.OW >= 32 ? ilog2_exact(d.OW / 32) : 0;
                 const bool up = d.mode == VD_B_CONV3_UP;
-#define VD_WPG(R_)                                                                                               \
-    do {                                                                                                         \
-        if (up)                                                                                                  \
-            hipLaunchKernelGGL((wgrad_patch_gen_kernel<R_, 2, 32>), grid, dim3(NT), 0, st, d, kk_per, ohs, sgs);     \
-        else                                                                                                     \
-            hipLaunchKernelGGL((wgrad_patch_gen_kernel<R_, 0, 32>), grid, dim3(NT), 0, st, d, kk_per, ohs, sgs);     \
-    } while (0)
-                if (d.OW == 4)
-                    VD_WPG(8);
-                else if (d.OW == 8)
-                    VD_WPG(4);
-                else
-                    VD_WPG(1);
-#undef VD_WPG
-            } else if (d.OW == 32 && d.mode == VD_B_CONV3)
-                hipLaunchKernelGGL((wgrad_patch_kernel<32, 0>), grid, dim3(NT), 0, st, d, kk_per);
-            else if (d.OW == 32)
-                hipLaunchKernelGGL((wgrad_patch_kernel<32, 2>), grid, dim3(NT), 0, st, d, kk_per);
-            else if (d.mode == VD_B_CONV3)
-                hipLaunchKernelGGL((wgrad_patch_kernel<16, 0>), grid, dim3(NT), 0, st, d, kk_per);
-            else
-                hipLaunchKernelGGL((wgrad_patch_kernel<16, 2>), grid, dim3(NT), 0, st, d, kk_per);
+                if (d.OW == 4 && up) VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<8, 2, 32>), grid, dim3(NT), 0, st, d, kk_per, ohs, sgs);
+                else if (d.OW == 4) VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<8, 0, 32>), grid, dim3(NT), 0, st, d, kk_per, ohs, sgs);
+                else if (d.OW == 8 && up) VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<4, 2, 32>), grid, dim3(NT), 0, st, d, kk_per, ohs, sgs);
+                else if (d.OW == 8) VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<4, 0, 32>), grid, dim3(NT), 0, st, d, kk_per, ohs, sgs);
+                else if (up) VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<1, 2, 32>), grid, dim3(NT), 0, st, d, kk_per, ohs, sgs);
+                else VD_LAUNCH_OR_NAME(name, (wgrad_patch_gen_kernel<1, 0, 32>), grid, dim3(NT), 0, st, d, kk_per, ohs, sgs);
+            } else if (d.OW == 32 && d.mode == VD_B_CONV3) VD_LAUNCH_OR_NAME(name, (wgrad_patch_kernel<32, 0>), grid, dim3(NT), 0, st, d, kk_per);
+            else if (d.OW == 32) VD_LAUNCH_OR_NAME(name, (wgrad_patch_kernel<32, 2>), grid, dim3(NT), 0, st, d, kk_per);
+            else if (d.mode == VD_B_CONV3) VD_LAUNCH_OR_NAME(name, (wgrad_patch_kernel<16, 0>), grid, dim3(NT), 0, st, d, kk_per);
+            else VD_LAUNCH_OR_NAME(name, (wgrad_patch_kernel<16, 2>), grid, dim3(NT), 0, st, d, kk_per);
             break;
         }
         case 6: {
             const int parts = wgrad_small_parts(d);
             const dim3 grid(parts * vd_cdiv(d.M <= 4 ? d.C : d.M, 32));
-            if (d.M <= 4) hipLaunchKernelGGL((wgrad_small_kernel<true>), grid, dim3(256), 0, st, d);
-            else hipLaunchKernelGGL((wgrad_small_kernel<false>), grid, dim3(256), 0, st, d);
+            if (d.M <= 4) VD_LAUNCH_OR_NAME(name, (wgrad_small_kernel<true>), grid, dim3(256), 0, st, d);
+            else VD_LAUNCH_OR_NAME(name, (wgrad_small_kernel<false>), grid, dim3(256), 0, st, d);
+            if (name) return vd_name_append(name, "(+colsum)") + tile;
             VD_LAUNCH_CHECK("vd_conv_wgrad/direct");
             hipLaunchKernelGGL(colsum_kernel, dim3(vd_cdiv(d.M * Ncols, 64)), dim3(256), 0, st, d.ws, d.dW, parts, d.M * Ncols,
                                (int64_t)d.M * Ncols, d.accumulate);
@@ -2469,15 +2457,15 @@ extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) {
             return 0;
         }
         case 5:
-            hipLaunchKernelGGL(wgrad1x1_bx3_kernel, dim3(vd_cdiv(d.M, 128) * vd_cdiv(d.C, 128), splits), dim3(NT), 0, st, d, kk_per);
-            rc = 0;
+            VD_LAUNCH_OR_NAME(name, wgrad1x1_bx3_kernel, dim3(vd_cdiv(d.M, 128) * vd_cdiv(d.C, 128), splits), dim3(NT), 0, st, d, kk_per);
             break;
-        case 1: rc = launch_wgrad_t<2, 2>(d, splits, kk_per, st); break;
-        case 2: rc = launch_wgrad_t<1, 2>(d, splits, kk_per, st); break;
-        case 3: rc = launch_wgrad_t<1, 1>(d, splits, kk_per, st); break;
+        case 1: rc = launch_wgrad_t<2, 2>(d, splits, kk_per, st, name); break;
+        case 2: rc = launch_wgrad_t<1, 2>(d, splits, kk_per, st, name); break;
+        case 3: rc = launch_wgrad_t<1, 1>(d, splits, kk_per, st, name); break;
         default: vd_set_error("vd_conv_wgrad: bad tile %d", tile); return VD_EINVAL;
     }
     if (rc) return rc;
+    if (name) return vd_name_append(name, "(+slab_reduce)") + tile;      // (recorded with the slab reduction whether or not this problem splits)
     VD_LAUNCH_CHECK("vd_conv_wgrad");
     if (splits > 1 && tile == 4) {
         const int64_t n = (int64_t)d.M * Ncols;
@@ -2496,6 +2484,13 @@ extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) {
         VD_LAUNCH_CHECK("vd_conv_wgrad/reduce");
     }
     return 0;
+}
+
+extern "C" int vd_conv_wgrad(const vd_wgrad_desc* desc, void* stream) { return wgrad_run(desc, (hipStream_t)stream, nullptr); }
+
+extern "C" int vd_conv_wgrad_kernel_name(const vd_wgrad_desc* desc, char* name, int name_len) {
+    char buf[VD_NAME_LEN] = "";
+    return name_out(wgrad_run(desc, nullptr, buf), buf, name, name_len);
 }
 
 // ---- grouped weight gradients -----------------------------------------------------------------------------------------------
@@ -2641,72 +2636,76 @@ extern "C" int vd_conv_wgrad_group_rebase(void* dev_table, int n, float* ws, voi
     return 0;
 }
 
-extern "C" int vd_conv_wgrad_group_launch(const void* dev_table, int n, int cls, int blocks, int rblocks, void* stream) {
-    VD_REQUIRE(dev_table && n > 0 && blocks > 0 && rblocks >= 0, "vd_conv_wgrad_group_launch: bad args");
+// vd_conv_wgrad_group_launch (name == NULL) and vd_conv_wgrad_group_kernel_name: one switch, as gemm_run
+static int wgrad_group_run(const void* dev_table, int n, int cls, int blocks, int rblocks, hipStream_t st, char* name) {
+    VD_REQUIRE(name || (dev_table && n > 0 && blocks > 0 && rblocks >= 0), "vd_conv_wgrad_group_launch: bad args");
     const vd_wgrad_job* jobs = reinterpret_cast<const vd_wgrad_job*>(dev_table);
-    hipStream_t st = (hipStream_t)stream;
     const dim3 grid(blocks);
     switch (cls) {
         case VD_WG_ONE + 1000: {
-            static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<true>),
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
-            VD_REQUIRE(attr1 == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
-            hipLaunchKernelGGL(wgrad1x1_wide_group_kernel<true>, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
-            break;
-        }
-        case VD_WG_ONE + 4 * 32 + 0: case VD_WG_ONE + 4 * 32 + 2: case VD_WG_ONE + 4 * 16 + 0: case VD_WG_ONE + 4 * 16 + 2:
-        case VD_WG_ONE + 4 * 8 + 0: case VD_WG_ONE + 4 * 8 + 2: {
-            const int wc = (cls - VD_WG_ONE) / 4;
-            const bool up = (cls - VD_WG_ONE) & 2;
-            if (wc == 32) {
-                if (up) hipLaunchKernelGGL((wgrad_k32_group_kernel<32, 2, true>), grid, dim3(NT), 0, st, jobs, n);
-                else hipLaunchKernelGGL((wgrad_k32_group_kernel<32, 0, true>), grid, dim3(NT), 0, st, jobs, n);
-            } else if (wc == 16) {
-                if (up) hipLaunchKernelGGL((wgrad_k32_group_kernel<16, 2, true>), grid, dim3(NT), 0, st, jobs, n);
-                else hipLaunchKernelGGL((wgrad_k32_group_kernel<16, 0, true>), grid, dim3(NT), 0, st, jobs, n);
-            } else {
-                if (up) hipLaunchKernelGGL((wgrad_k32_group_kernel<8, 2, true>), grid, dim3(NT), 0, st, jobs, n);
-                else hipLaunchKernelGGL((wgrad_k32_group_kernel<8, 0, true>), grid, dim3(NT), 0, st, jobs, n);
+            if (!name) {
+                static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<true>),
+                                                                    hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
+                VD_REQUIRE(attr1 == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
             }
+            VD_LAUNCH_OR_NAME(name, wgrad1x1_wide_group_kernel<true>, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
             break;
         }
+        case VD_WG_ONE + 4 * 32 + 0: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<32, 0, true>), grid, dim3(NT), 0, st, jobs, n); break;
+        case VD_WG_ONE + 4 * 32 + 2: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<32, 2, true>), grid, dim3(NT), 0, st, jobs, n); break;
+        case VD_WG_ONE + 4 * 16 + 0: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<16, 0, true>), grid, dim3(NT), 0, st, jobs, n); break;
+        case VD_WG_ONE + 4 * 16 + 2: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<16, 2, true>), grid, dim3(NT), 0, st, jobs, n); break;
+        case VD_WG_ONE + 4 * 8 + 0: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<8, 0, true>), grid, dim3(NT), 0, st, jobs, n); break;
+        case VD_WG_ONE + 4 * 8 + 2: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<8, 2, true>), grid, dim3(NT), 0, st, jobs, n); break;
         case VD_WG_ONE + 3000 + 4 * 32: case VD_WG_ONE + 3000 + 4 * 16: case VD_WG_ONE + 3000 + 4 * 8: case VD_WG_ONE + 3000 + 4 * 32 + 2:
         case VD_WG_ONE + 3000 + 4 * 16 + 2: case VD_WG_ONE + 3000 + 4 * 8 + 2:
-            VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - VD_WG_ONE - 3000) / 4, (cls - VD_WG_ONE - 3000) & 2, blocks, st, true) == 0,
+            VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - VD_WG_ONE - 3000) / 4, (cls - VD_WG_ONE - 3000) & 2, blocks, st, true, name) == 0,
                        "vd_conv_wgrad_group_launch: no pre-split kernel for class %d", cls);
             break;
         case 1000: {
-            static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<>),
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
-            VD_REQUIRE(attr == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
-            hipLaunchKernelGGL(wgrad1x1_wide_group_kernel<>, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
+            if (!name) {
+                static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_group_kernel<>),
+                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, W1X1_WIDE_LDS);
+                VD_REQUIRE(attr == hipSuccess, "vd_conv_wgrad_group_launch: cannot reserve %d bytes of LDS", W1X1_WIDE_LDS);
+            }
+            VD_LAUNCH_OR_NAME(name, wgrad1x1_wide_group_kernel<>, grid, dim3(512), W1X1_WIDE_LDS, st, jobs, n);
             break;
         }
-        case 4 * 32 + 0: hipLaunchKernelGGL((wgrad_k32_group_kernel<32, 0>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 32 + 2: hipLaunchKernelGGL((wgrad_k32_group_kernel<32, 2>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 32 + 1: hipLaunchKernelGGL((wgrad_bx3_group_kernel<32, 0, true>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 32 + 3: hipLaunchKernelGGL((wgrad_bx3_group_kernel<32, 2, true>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 16 + 0: hipLaunchKernelGGL((wgrad_k32_group_kernel<16, 0>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 16 + 2: hipLaunchKernelGGL((wgrad_k32_group_kernel<16, 2>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 8 + 0: hipLaunchKernelGGL((wgrad_k32_group_kernel<8, 0>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 8 + 2: hipLaunchKernelGGL((wgrad_k32_group_kernel<8, 2>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 4 * 4 + 0: hipLaunchKernelGGL((wgrad_bx3_group_kernel<4, 0>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 32 + 0: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<32, 0>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 32 + 2: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<32, 2>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 32 + 1: VD_LAUNCH_OR_NAME(name, (wgrad_bx3_group_kernel<32, 0, true>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 32 + 3: VD_LAUNCH_OR_NAME(name, (wgrad_bx3_group_kernel<32, 2, true>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 16 + 0: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<16, 0>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 16 + 2: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<16, 2>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 8 + 0: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<8, 0>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 8 + 2: VD_LAUNCH_OR_NAME(name, (wgrad_k32_group_kernel<8, 2>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 4 * 4 + 0: VD_LAUNCH_OR_NAME(name, (wgrad_bx3_group_kernel<4, 0, false>), grid, dim3(NT), 0, st, jobs, n); break;
         case 3000 + 4 * 32: case 3000 + 4 * 16: case 3000 + 4 * 8: case 3000 + 4 * 32 + 2: case 3000 + 4 * 16 + 2: case 3000 + 4 * 8 + 2:
-            VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - 3000) / 4, (cls - 3000) & 2, blocks, st, false) == 0,
+            VD_REQUIRE(vd_launch_wgrad_ps_group(dev_table, n, (cls - 3000) / 4, (cls - 3000) & 2, blocks, st, false, name) == 0,
                        "vd_conv_wgrad_group_launch: no pre-split kernel for class %d", cls);
             break;
-        case 2000 + 33: hipLaunchKernelGGL((wgrad_bx3_group_kernel<32, 4, true>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 2000 + 32: hipLaunchKernelGGL((wgrad_bx3_group_kernel<32, 4>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 2000 + 16: hipLaunchKernelGGL((wgrad_bx3_group_kernel<16, 4>), grid, dim3(NT), 0, st, jobs, n); break;
-        case 2000 + 8: hipLaunchKernelGGL((wgrad_bx3_group_kernel<8, 4>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 2000 + 33: VD_LAUNCH_OR_NAME(name, (wgrad_bx3_group_kernel<32, 4, true>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 2000 + 32: VD_LAUNCH_OR_NAME(name, (wgrad_bx3_group_kernel<32, 4, false>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 2000 + 16: VD_LAUNCH_OR_NAME(name, (wgrad_bx3_group_kernel<16, 4, false>), grid, dim3(NT), 0, st, jobs, n); break;
+        case 2000 + 8: VD_LAUNCH_OR_NAME(name, (wgrad_bx3_group_kernel<8, 4, false>), grid, dim3(NT), 0, st, jobs, n); break;
         default: vd_set_error("vd_conv_wgrad_group_launch: unknown kernel class %d", cls); return VD_EINVAL;
     }
+    if (name) return vd_name_append(name, "(+group_reduce)");      // (recorded with the slab reduction whether or not this launch needs one)
     VD_LAUNCH_CHECK("vd_conv_wgrad_group_launch");
     if (rblocks > 0) {
         hipLaunchKernelGGL(wgrad_group_reduce_kernel, dim3(rblocks), dim3(256), 0, st, jobs, n);
         VD_LAUNCH_CHECK("vd_conv_wgrad_group_launch/reduce");
     }
     return 0;
+}
+
+extern "C" int vd_conv_wgrad_group_launch(const void* dev_table, int n, int cls, int blocks, int rblocks, void* stream) {
+    return wgrad_group_run(dev_table, n, cls, blocks, rblocks, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int vd_conv_wgrad_group_kernel_name(int cls, char* name, int name_len) {
+    char buf[VD_NAME_LEN] = "";
+    return name_out(wgrad_group_run(nullptr, 0, cls, 0, 0, nullptr, buf), buf, name, name_len);
 }
 
 // Workspace floats vd_conv_wgrad needs for the given problem (0 when no split is chosen).

@@ -381,9 +381,9 @@ bool vd_gemm1x1_k32p_pick(const vd_gemm_desc& d) {
     return 4 * nt >= 3 * rounds * 256;                // every round of 256 workgroup slots at least 75 % full
 }
 
-int vd_launch_gemm1x1_k32p(const vd_gemm_desc& d, hipStream_t st) {
+int vd_launch_gemm1x1_k32p(const vd_gemm_desc& d, hipStream_t st, char* name) {
     static int n_cu = 0;
-    if (n_cu == 0) {
+    if (!name && n_cu == 0) {
         int dev = 0;
         hipDeviceProp_t p;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return -1;
@@ -400,10 +400,10 @@ int vd_launch_gemm1x1_k32p(const vd_gemm_desc& d, hipStream_t st) {
     a.tiles_m = vd_cdiv(d.M, big_m ? 256 : 128);
     a.n_tiles = a.tiles_m * (d.N / (big_m ? 128 : 256));
     const int grid = a.n_tiles < n_cu ? ((a.n_tiles + 7) & ~7) : n_cu;
-    if (d.math == 2) hipLaunchKernelGGL((gemm1x1_k32p_kernel<true, 128>), dim3(grid), dim3(512), 0, st, a);
-    else if (d.math == 3 && big_m) hipLaunchKernelGGL((gemm1x1_k32p_kernel<false, 256, true>), dim3(grid), dim3(512), 0, st, a);
-    else if (d.math == 3) hipLaunchKernelGGL((gemm1x1_k32p_kernel<false, 128, true>), dim3(grid), dim3(512), 0, st, a);
-    else if (big_m) hipLaunchKernelGGL((gemm1x1_k32p_kernel<false, 256>), dim3(grid), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((gemm1x1_k32p_kernel<false, 128>), dim3(grid), dim3(512), 0, st, a);
+    if (d.math == 2) VD_LAUNCH_OR_NAME(name, (gemm1x1_k32p_kernel<true, 128>), dim3(grid), dim3(512), 0, st, a);
+    else if (d.math == 3 && big_m) VD_LAUNCH_OR_NAME(name, (gemm1x1_k32p_kernel<false, 256, true>), dim3(grid), dim3(512), 0, st, a);
+    else if (d.math == 3) VD_LAUNCH_OR_NAME(name, (gemm1x1_k32p_kernel<false, 128, true>), dim3(grid), dim3(512), 0, st, a);
+    else if (big_m) VD_LAUNCH_OR_NAME(name, (gemm1x1_k32p_kernel<false, 256>), dim3(grid), dim3(512), 0, st, a);
+    else VD_LAUNCH_OR_NAME(name, (gemm1x1_k32p_kernel<false, 128>), dim3(grid), dim3(512), 0, st, a);
     return 0;
 }

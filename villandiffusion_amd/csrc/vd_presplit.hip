@@ -748,7 +748,7 @@ extern "C" int vd_groupnorm_bwd_presplit(const float* dy, const float* x, const 
 }
 
 // vd_gemm.hip's grouped launch (class 3000 + 4 W + 2 * upsample-fused): both operands pre-split; one: one bf16 product per term (math = 3)
-int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks, hipStream_t st, bool one) {
+int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks, hipStream_t st, bool one, char* name) {
     const vd_wgrad_job* jb = reinterpret_cast<const vd_wgrad_job*>(jobs);
     // 4.5 KB of (unused) dynamic LDS on top of the kernel's 76 KB: ONE workgroup per CU instead of two (2 x 80.5 KB > 160 KB).  Two of them hold a CU's whole
     // LDS and register file for ~90 us at a time, and the backward pass on the main stream -- latency-bound 8x8 / 4x4 kernels, GroupNorm passes -- only gets a CU
@@ -759,10 +759,10 @@ int vd_launch_wgrad_ps_group(const void* jobs, int n, int W, int up, int blocks,
     static const int pad = getenv("VD_WGRAD_PS_LDS_PAD") ? atoi(getenv("VD_WGRAD_PS_LDS_PAD")) : 4608;
 #define VD_WG_PS(WW)                                                                                                \
     case WW:                                                                                                        \
-        if (one && up) hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 2, true>), dim3(blocks), dim3(256), pad, st, jb, n); \
-        else if (one) hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 0, true>), dim3(blocks), dim3(256), pad, st, jb, n);  \
-        else if (up) hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 2>), dim3(blocks), dim3(256), pad, st, jb, n);         \
-        else hipLaunchKernelGGL((wgrad_ps_group_kernel<WW, 0>), dim3(blocks), dim3(256), pad, st, jb, n);            \
+        if (one && up) VD_LAUNCH_OR_NAME(name, (wgrad_ps_group_kernel<WW, 2, true>), dim3(blocks), dim3(256), pad, st, jb, n); \
+        else if (one) VD_LAUNCH_OR_NAME(name, (wgrad_ps_group_kernel<WW, 0, true>), dim3(blocks), dim3(256), pad, st, jb, n);  \
+        else if (up) VD_LAUNCH_OR_NAME(name, (wgrad_ps_group_kernel<WW, 2>), dim3(blocks), dim3(256), pad, st, jb, n);         \
+        else VD_LAUNCH_OR_NAME(name, (wgrad_ps_group_kernel<WW, 0>), dim3(blocks), dim3(256), pad, st, jb, n);            \
         return 0;
     switch (W) {
         VD_WG_PS(32) VD_WG_PS(16) VD_WG_PS(8)

@@ -51,9 +51,11 @@ PROTOTYPES = {
     "vd_gemm": (_i32, [C.POINTER(GemmDesc), _vp]),
     "vd_gemm_tile": (_i32, [C.POINTER(GemmDesc)]),
     "vd_gemm_ws_floats": (_i64, [C.POINTER(GemmDesc)]),
+    "vd_gemm_kernel_name": (_i32, [C.POINTER(GemmDesc), C.c_char_p, _i32]),
     "vd_conv_wgrad": (_i32, [C.POINTER(WgradDesc), _vp]),
     "vd_conv_wgrad_plan": (_i32, [C.POINTER(WgradDesc), C.POINTER(_i32), C.POINTER(_i32)]),
     "vd_conv_wgrad_ws_floats": (_i64, [C.POINTER(WgradDesc)]),
+    "vd_conv_wgrad_kernel_name": (_i32, [C.POINTER(WgradDesc), C.c_char_p, _i32]),
     "vd_presplit_pack": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp]),
     "vd_presplit_unpack": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp]),
     "vd_groupnorm_fwd_presplit_ok": (_i32, [_i32, _i32, _i32]),
@@ -62,6 +64,7 @@ PROTOTYPES = {
     "vd_conv_wgrad_group_class": (_i32, [C.POINTER(WgradDesc)]),
     "vd_conv_wgrad_group_job_bytes": (_i64, []),
     "vd_conv_wgrad_group_variant": (_i32, [_i32]),
+    "vd_conv_wgrad_group_kernel_name": (_i32, [_i32, C.c_char_p, _i32]),
     "vd_conv_wgrad_group_plan": (_i32, [C.POINTER(WgradDesc), _i32, _vp, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
     "vd_conv_wgrad_group_rebase": (_i32, [_vp, _i32, _vp, _vp]),
     "vd_conv_wgrad_group_launch": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp]),
@@ -165,7 +168,7 @@ def load() -> C.CDLL:
     for name, (res, args) in PROTOTYPES.items():
         fn = getattr(lib, name)       # AttributeError here = header/library mismatch: fail loudly
         fn.restype, fn.argtypes = res, args
-    if lib.vd_abi_version() != 11:
+    if lib.vd_abi_version() != 12:
         raise VillanHipError("libvillan_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -7,6 +7,7 @@ whose batch stride may be larger than C*H*W (channel slices of a concat buffer).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 from typing import Optional, Sequence
@@ -26,8 +27,12 @@ def _lib():
 # ---- optional per-launch timing of the MFMA kernels (bench.py roofline leg): HIP events on the launch stream ----
 _PROF = None          # list of (kernel_symbol, algorithmic_flops, start_event, end_event) while enabled
 
-_B_NAMES = {0: "PLAIN", 1: "KCONTIG", 2: "CONV3", 3: "CONV3_T", 4: "CONV3_S2", 5: "CONV3_UP", 6: "CONV3_DIL", 7: "CONVG"}
-_TILE_NAMES = {1: "128x128", 2: "64x128", 3: "64x64", 4: "patch128x128"}
+
+def _kernel_name(query, what) -> str:
+    """The recorded name of a launch: the library writes the instantiation its own launch branch names (vd_*_kernel_name, host only)."""
+    buf = C.create_string_buffer(128)
+    L.check(min(query(what, buf, len(buf)), 0), "kernel name query")
+    return buf.value.decode()
 
 
 def profile_start():
@@ -139,39 +144,86 @@ def groupnorm_fwd_presplit(x, gamma, beta, y: PreSplit, mean, rstd, G, eps, silu
     return y
 
 
-_PS_CONV_OK = {}
+# ---- shape-only questions to the library's planners (vd_gemm_tile, vd_conv_wgrad_plan, vd_conv_wgrad_group_class: host functions, no device): the one
+# place that picks a kernel.  The predicates build a placeholder descriptor -- contiguous NCHW at 16-byte aligned dummy addresses -- and ask once per shape.
+_FAKE_PTR = 0x10000
+_BX3_TILES = (8, 12, 15, 16, 18, 20)           # vd_gemm_tile() of the split-precision 3x3 convolutions; 9 / 11 / 13 / 19: 1x1 and plain products; 10: activations
 
 
+def _src_side(mode, s):
+    """Side of the gather's source under an output side."""
+    return s // 2 if mode == B_CONV3_UP else (2 * s if mode == B_CONV3_S2 else s)
+
+
+def conv_query_desc(M, Cc, OH, OW, mode, nb=1, **flags) -> GemmDesc:
+    """vd_gemm_desc of a 3x3 convolution Cc -> M with OH x OW outputs and a packed weight operand; flags: further fields (math, pool2, b_presplit, ...)."""
+    H, W = _src_side(mode, OH), _src_side(mode, OW)
+    d = GemmDesc()
+    d.A = d.B = d.D = d.a_packed = _FAKE_PTR
+    d.a_packed_mpad = (M + 127) // 128 * 128
+    d.M, d.N, d.K, d.NP = M, nb * OH * OW, Cc * 9, OH * OW
+    d.a_mode, d.b_mode, d.alpha = A_ROW, mode, 1.0
+    d.C, d.H, d.W, d.OH, d.OW = Cc, H, W, OH, OW
+    d.lda, d.b_bstride = Cc * 9, Cc * H * W
+    d.ldd = (OH // 2) * (OW // 2) if flags.get("pool2") else OH * OW          # (pool2 writes D at half resolution)
+    d.d_bstride = M * d.ldd
+    for k, v in flags.items():
+        setattr(d, k, v)
+    return d
+
+
+def product_query_desc(M, K, NP, nb=1, a_mode=A_ROW, b_mode=B_PLAIN, act=False) -> GemmDesc:
+    """vd_gemm_desc of D[b] = A @ B[b] ([M, K] x [K, NP]).  act=False: shared A with a packed operand (1x1 convolutions, projections);
+    act=True: a product of two activation matrices -- per-batch A, math = 1, nothing packed."""
+    d = GemmDesc()
+    d.A = d.B = d.D = _FAKE_PTR
+    d.M, d.N, d.K, d.NP = M, nb * NP, K, NP
+    d.a_mode, d.b_mode, d.alpha = a_mode, b_mode, 1.0
+    d.lda = K if a_mode == A_ROW else M
+    d.ldb = K if b_mode == B_KCONTIG else NP
+    d.b_bstride, d.ldd, d.d_bstride = K * NP, NP, M * NP
+    if act:
+        d.math, d.a_bstride = 1, M * K
+    else:
+        d.a_packed, d.a_packed_mpad = _FAKE_PTR, (M + 127) // 128 * 128
+    return d
+
+
+def wgrad_query_desc(M, Cc, OH, OW, mode, nb=1, math_mode=1, **flags) -> WgradDesc:
+    """vd_wgrad_desc of the weight gradient of a convolution Cc -> M with OH x OW outputs (mode B_PLAIN: 1x1, else 3x3)."""
+    d = WgradDesc()
+    d.dY = d.X = d.dW = _FAKE_PTR
+    d.M, d.C, d.T, d.nb, d.NP = M, Cc, 1 if mode == B_PLAIN else 9, nb, OH * OW
+    d.H, d.W, d.OH, d.OW = _src_side(mode, OH), _src_side(mode, OW), OH, OW
+    d.mode, d.math = mode, math_mode
+    d.dy_bstride, d.x_bstride = M * OH * OW, Cc * d.H * d.W
+    for k, v in flags.items():
+        setattr(d, k, v)
+    return d
+
+
+def _gemm_tile(d: GemmDesc) -> int:
+    return int(L.load().vd_gemm_tile(C.byref(d)))
+
+
+def _wgrad_tile(d: WgradDesc) -> int:
+    tile, splits = C.c_int32(0), C.c_int32(0)
+    L.load().vd_conv_wgrad_plan(C.byref(d), C.byref(tile), C.byref(splits))
+    return tile.value
+
+
+@functools.lru_cache(maxsize=None)
 def conv_presplit_ok(Bn: int, Cin: int, Cout: int, OH: int, OW: int, mode: int) -> bool:
     """Would conv3x3(PreSplit input [Bn, Cin, ..] -> [Bn, Cout, OH, OW], mode, a_packed=...) be taken by the persistent 16x16x32 kernel, the only
-    reader of pre-split images?  (vd_gemm_tile() == 18 with b_presplit = 1; asked once per shape.)"""
-    key = (Bn, Cin, Cout, OH, OW, mode)
-    ok = _PS_CONV_OK.get(key)
-    if ok is None:
-        H, W = (OH // 2, OW // 2) if mode == B_CONV3_UP else (OH, OW)
-        d = GemmDesc()
-        d.A = d.B = d.D = d.a_packed = 64                  # (non-null placeholders: vd_gemm_tile() only looks at shapes, strides and alignment)
-        d.a_packed_mpad = (Cout + 127) // 128 * 128
-        d.M, d.N, d.K = Cout, Bn * OH * OW, Cin * 9
-        d.a_mode, d.b_mode, d.NP = A_ROW, mode, OH * OW
-        d.C, d.H, d.W, d.OH, d.OW = Cin, H, W, OH, OW
-        d.alpha = 1.0
-        d.lda, d.b_bstride, d.ldd, d.d_bstride = Cin * 9, Cin * H * W, OH * OW, Cout * OH * OW
-        d.b_presplit = 1
-        ok = _PS_CONV_OK[key] = int(_lib().vd_gemm_tile(C.byref(d))) == 18
-    return ok
+    reader of pre-split images?  (vd_gemm_tile() == 18 with b_presplit = 1.)"""
+    return _gemm_tile(conv_query_desc(Cout, Cin, OH, OW, mode, Bn, b_presplit=1)) == 18
 
 
+@functools.lru_cache(maxsize=None)
 def wgrad_presplit_ok(Bn: int, Cin: int, Cout: int, S: int, mode: int = B_CONV3) -> bool:
     """Is there a grouped pre-split weight-gradient kernel for a 3x3 convolution Cin -> Cout with S x S OUTPUTS (mode B_CONV3 or B_CONV3_UP)?"""
-    d = WgradDesc()
-    d.dY = d.X = d.dW = 64
-    d.M, d.C, d.T, d.nb, d.NP = Cout, Cin, 9, Bn, S * S
-    d.OH = d.OW = S
-    d.H = d.W = S // 2 if mode == B_CONV3_UP else S
-    d.mode, d.accumulate, d.math, d.presplit = mode, 1, 1, 3
-    d.dy_bstride, d.x_bstride = Cout * S * S, Cin * d.H * d.W
-    return int(_lib().vd_conv_wgrad_group_class(C.byref(d))) >= 3000
+    d = wgrad_query_desc(Cout, Cin, S, S, mode, Bn, accumulate=1, presplit=3)
+    return int(L.load().vd_conv_wgrad_group_class(C.byref(d))) >= 3000
 
 
 def groupnorm_bwd_presplit(dy, x, mean, rstd, gamma, beta, dx, dx_ps, dgamma_ws, dbeta_ws, G, silu, extra=None, extra2=None, rowsum=None,
@@ -312,40 +364,7 @@ def gemm(A, B, D, *, M, N, K, a_mode=A_ROW, b_mode=B_PLAIN, NP=None, lda=0, a_bs
         a_elems = M * K * (N // d.NP if a_bstride else 1)
     d_elems = M * N // (4 if pool2 else 1)
     nbytes = 4.0 * (b_elems + d_elems * (2 if residual is not None else 1) + a_elems)
-    tl = LAST_GEMM_TILE
-    if tl == 10:
-        name = f"gemm_bx3_act_kernel<{int(a_mode == A_ROW)}, {int(b_mode == B_KCONTIG)}>"
-    elif tl == 19:
-        # (the 256 x 128 tile where M % 256 == 0: vd_launch_gemm1x1_k32p; symbol names as rocprofv3 prints them)
-        big = d.math != 2 and M % 256 == 0 and N % 128 == 0
-        name = ("gemm1x1_k32p_kernel<true, 128>" if d.math == 2 else
-                f"gemm1x1_k32p_kernel<false, {256 if big else 128}{', true' if d.math == 3 else ''}>")
-    elif tl in (9, 11, 13):
-        name = "gemm_bx3_persist_kernel" if tl == 11 else f"gemm_bx3_kernel<{512 if tl == 13 else 256}>"
-    elif tl == 18:          # the persistent kernel: template width 16 (16x16 images) or 32 (8-row x 32-column segments of any image); image width beside it
-        md = (3 if gn_ss is not None else 0) if b_mode == B_CONV3 else (1 if b_mode == B_CONV3_T else 2)
-        name = (f"conv3_k32p_kernel<{16 if d.OW == 16 else 32}, {md}, true, true, {'true' if d.math == 2 else 'false'}, {'true' if d.b_presplit else 'false'}"
-                + (", true>" if d.math == 3 else ">")
-                + (f"@{d.OW}" if d.OW > 32 else ""))
-    elif tl == 20:          # the whole-K kernel of the 8x8 / 4x4 levels
-        imgs = 2 if d.OW == 8 else 4
-        name = f"conv3_sm_kernel<{d.OW}, {1 if b_mode == B_CONV3_T else 0}, {imgs}, 1{', true' if d.math == 3 else ''}>"
-    elif tl in (8, 12, 15, 16):
-        md = (3 if gn_ss is not None else 0) if b_mode == B_CONV3 else (1 if b_mode == B_CONV3_T else (4 if b_mode == B_CONV3_S2 else 2))
-        name = f"conv3_bx3_kernel<{d.OW if d.OW <= 64 else 128}, {md}, {4 if tl == 15 else 2}, {256 if tl == 8 else 512}, 2>"
-    elif tl in (4, 6):     # symbol names as rocprofv3 prints them
-        tw = d.OW if d.OW <= 64 else 128          # tile width (template W): row segments of wider images
-        md = (3 if gn_ss is not None else 0) if b_mode == B_CONV3 else (1 if b_mode == B_CONV3_T else (4 if b_mode == B_CONV3_S2 else 2))
-        name = f"conv3_patch_kernel<{tw}, {md}, {4 if tl == 6 else 2}>"
-    elif tl == 5:
-        name = f"gemm_plain_kernel<{a_mode}>"
-    elif tl == 7:
-        few = d.W % 4 == 0 and d.C >= 16 and d.b_bstride % 4 == 0 and d.d_bstride % 4 == 0 and d.ldd % 4 == 0      # fewout_eligible() of vd_gemm.hip
-        # (B_CONV3_T: the flipped-tap form, conv_in's input gradient -- it has no LDS-patch partner)
-        name = (f"conv3_fewout_kernel<4, 8, {'true' if b_mode == B_CONV3_T else 'false'}>" if few or b_mode == B_CONV3_T
-                else f"conv3_smallm_kernel<{32 if d.W % 32 == 0 else 16}, 4>")
-    else:
-        name = f"gemm_kernel<{_TILE_NAMES[tl]},{'ROW' if a_mode == A_ROW else 'COL'},{_B_NAMES[b_mode]}>"
+    name = _kernel_name(lib.vd_gemm_kernel_name, C.byref(d))
     _PROF.append({"name": name, "flops": flops, "bytes": nbytes, "e0": e0, "e1": e1, "kind": "mfma", "shape": (M, K, d.NP, N // d.NP, d.OH, d.OW)})
     return D
 
@@ -400,21 +419,18 @@ def conv3_pack_weights_multi(table, n_jobs, total_blocks):
 WEIGHTS_EPOCH = 0
 
 
+@functools.lru_cache(maxsize=None)
 def bx3_eligible(M, Cc, OH, OW, mode) -> bool:
-    """Problems the split-precision convolution kernel takes (vd_gemm_desc.a_packed)."""
-    if mode == B_CONV3_S2:                                  # stride 2 (OH, OW: the OUTPUT, half the input): square 4x4 .. 32x32 outputs, 64 / 128 k wide ones
-        return Cc % 16 == 0 and M >= 64 and OH == OW and (OW in (4, 8, 16, 32, 64) or (OW >= 128 and OW % 128 == 0))
-    if mode not in (B_CONV3, B_CONV3_T, B_CONV3_UP) or Cc % 16 != 0 or M < 64 or (OW == 4 and mode == B_CONV3_UP):
-        return False
-    if OW == 64 or (OW >= 128 and OW % 128 == 0):           # row-segment tiles of wide images
-        return (OH * OW) % 128 == 0
-    return OH == OW and OW in (4, 8, 16, 32)
+    """Problems the split-precision convolution kernels take (vd_gemm_desc.a_packed; OH, OW: the OUTPUT)."""
+    return _gemm_tile(conv_query_desc(M, Cc, OH, OW, mode)) in _BX3_TILES
 
 
+@functools.lru_cache(maxsize=None)
 def bx3_pool2_eligible(M, Cc, OH, OW, nb) -> bool:
     """The split-precision stride-1 dgrad can add the 2x2 blocks of its output in the epilogue (vd_gemm_desc.pool2): 16x16 / 32x32 outputs
-    on an unsplit grid (>= 256 tiles of 128 channels x 128 pixels; below that the kernel splits the channel loop over workgroups)."""
-    return bx3_eligible(M, Cc, OH, OW, B_CONV3_T) and OH == OW and OW in (16, 32) and ((M + 127) // 128) * ((nb * OH * OW + 127) // 128) >= 256
+    on an unsplit grid (>= 256 tiles of 128 channels x 128 pixels; below that the kernel splits the channel loop over workgroups).  The persistent
+    kernel would also take it on the wider images it walks; the network keeps its separate 2x2 sum there, as it always has (OW <= 32)."""
+    return _gemm_tile(conv_query_desc(M, Cc, OH, OW, B_CONV3_T, nb, pool2=1)) in _BX3_TILES and OW <= 32
 
 
 GN_PART_WRITTEN = False
@@ -504,16 +520,17 @@ def attn_core_eligible(heads, head_dim, N) -> bool:
     return N == 256 and heads >= 1 and (head_dim in (32, 64, 128) or (head_dim > 0 and head_dim % 256 == 0))
 
 
+@functools.lru_cache(maxsize=None)
 def gemm_bx3_act_eligible(M, K, NP) -> bool:
-    """Products of two activation matrices (attention) the split-precision kernel takes (vd_gemm_desc.math = 1)."""
-    return NP % 128 == 0 and K % 16 == 0 and K >= 32 and M >= 64 and M % 4 == 0
+    """Products of two activation matrices (attention) the split-precision kernel takes (vd_gemm_desc.math = 1).  The callers do not say which
+    way A lies, so the question is asked for column-major A, the layout with the stricter rule (M % 4 == 0)."""
+    return _gemm_tile(product_query_desc(M, K, NP, a_mode=A_COL, act=True)) == 10
 
 
+@functools.lru_cache(maxsize=None)
 def gemm_bx3_eligible(M, K, NP, nb=None) -> bool:
-    """1x1 convolutions / plain products the split-precision GEMM kernel takes (vd_gemm_desc.a_packed, shared A); nb = batch items."""
-    if K % 16 != 0 or M < 64:
-        return False
-    return NP % 128 == 0 or (128 % NP == 0 and nb is not None and (nb * NP) % 128 == 0)
+    """1x1 convolutions / plain products the split-precision GEMM kernels take (vd_gemm_desc.a_packed, shared A); nb = batch items (None: one)."""
+    return _gemm_tile(product_query_desc(M, K, NP, nb or 1)) in (9, 11, 13, 19)
 
 
 def conv1x1(x, w2d, bias, out, residual=None, accumulate=False, tile=0, a_packed=None):
@@ -692,41 +709,10 @@ def conv_wgrad_group(descs: Sequence[WgradDesc], device):
         _CAPTURE_TABLES.append(ent["table"])              # a cache hit inside a capture: the graph reads this table too
     flops = sum(2.0 * d.M * d.C * d.T * d.nb * d.NP for d in descs)
     nbytes = sum(4.0 * (d.nb * d.M * d.NP + d.nb * d.C * d.H * d.W + d.M * d.C * d.T) for d in descs)
-    var = lib.vd_conv_wgrad_group_variant(ent["cls"])
-    if ent["cls"] > WGRAD_ONE:                                   # one bf16 product per term (math = 3): the ONE instantiations
-        bc = ent["cls"] - WGRAD_ONE
-        if bc >= 3000:
-            name = f"wgrad_ps_group_kernel<{(bc - 3000) // 4}, {(bc - 3000) & 2}, true>(+group_reduce)"
-        elif bc == 1000:
-            name = "wgrad1x1_wide_group_kernel<true>(+group_reduce)"
-        else:
-            name = f"wgrad_k32_group_kernel<{bc // 4}, {bc & 2}, true>(+group_reduce)"
-    elif ent["cls"] >= 3000:                                     # both operands pre-split: LDS-DMA + transposed reads (vd_presplit.hip)
-        name = f"wgrad_ps_group_kernel<{(ent['cls'] - 3000) // 4}, {(ent['cls'] - 3000) & 2}>(+group_reduce)"
-    elif ent["cls"] > 2000:                                      # stride-2 3x3 classes (2000 + output width; 2033: 32-pixel segments of wide outputs)
-        name = "wgrad_bx3_group_kernel<32, 4, true>(+group_reduce)" if ent["cls"] == 2033 else f"wgrad_bx3_group_kernel<{ent['cls'] - 2000}, 4, false>(+group_reduce)"
-    elif ent["cls"] == 1000:                                     # symbol names as rocprofv3 prints them
-        name = "wgrad1x1_wide_group_kernel(+group_reduce)"
-    elif var == 32:
-        name = f"wgrad_k32_group_kernel<{ent['cls'] // 4}, {ent['cls'] & 2}>(+group_reduce)"
-    else:
-        name = f"wgrad_bx3_group_kernel<{ent['cls'] // 4}, {ent['cls'] & 2}, {'true' if ent['cls'] & 1 else 'false'}>(+group_reduce)"
+    name = _kernel_name(lib.vd_conv_wgrad_group_kernel_name, ent["cls"]) if _PROF is not None else None
     _timed(name, flops, "mfma", lambda: L.check(
         lib.vd_conv_wgrad_group_launch(ent["table"].data_ptr(), n, ent["cls"], ent["blocks"], ent["rblocks"], _s()), "vd_conv_wgrad_group_launch"),
         nbytes=nbytes)
-
-
-def wgrad_single_name(OW, mode) -> str:
-    """The instantiation vd_conv_wgrad launches for a split-precision (math = 1) 3x3 weight gradient of tile 4 (the switch in vd_gemm.hip): stride 2 and
-    4x4 / wide stride-1 outputs run wgrad_bx3_kernel (32-pixel row segments from 64 pixels up), 8x8 / 16x16 / 32x32 stride-1 outputs wgrad_k32_kernel."""
-    if mode == B_CONV3_S2:
-        return f"wgrad_bx3_kernel<{min(OW, 32)}, 4{', true' if OW >= 64 else ''}>"
-    md = 2 if mode == B_CONV3_UP else 0
-    if OW >= 64:
-        return f"wgrad_bx3_kernel<32, {md}, true>"
-    if OW == 4:
-        return "wgrad_bx3_kernel<4, 0>"
-    return f"wgrad_k32_kernel<{OW}, {md}>"
 
 
 def conv_wgrad(dy, x, dw2d, mode, ws: Optional[torch.Tensor], accumulate=False, splits=0, tile=0, pad=0, math_mode=0):
@@ -745,18 +731,7 @@ def conv_wgrad(dy, x, dw2d, mode, ws: Optional[torch.Tensor], accumulate=False, 
     e0.record()
     L.check(lib.vd_conv_wgrad(C.byref(d), _s()), "vd_conv_wgrad")
     e1.record()
-    tl, sp = C.c_int32(0), C.c_int32(0)
-    lib.vd_conv_wgrad_plan(C.byref(d), C.byref(tl), C.byref(sp))
-    if tl.value == 6:
-        name = f"wgrad_small_kernel<{'true' if M <= 4 else 'false'}>(+colsum)"
-    elif tl.value == 5:
-        name = "wgrad1x1_bx3_kernel(+slab_reduce)"
-    elif tl.value == 4 and math_mode == 1:
-        name = wgrad_single_name(OW, mode) + "(+slab_reduce)"
-    elif tl.value == 4:
-        name = f"wgrad_patch_kernel<{OW}, {0 if mode == B_CONV3 else 2}>(+slab_reduce)"
-    else:
-        name = f"wgrad_kernel<{_TILE_NAMES[tl.value]},{_B_NAMES[mode]}>(+slab_reduce)"
+    name = _kernel_name(lib.vd_conv_wgrad_kernel_name, C.byref(d))
     _PROF.append({"name": name, "flops": 2.0 * M * Cc * T * Bn * OH * OW, "bytes": 4.0 * (dy.numel() + x.numel() + M * Cc * T),
                   "e0": e0, "e1": e1, "kind": "mfma"})
     return dw2d
@@ -770,27 +745,22 @@ def _wgrad_s2_split(OW) -> bool:
     return sel == "all" or (sel != "none" and OW >= 32)
 
 
+@functools.lru_cache(maxsize=None)
+def _wgrad_split_kernel(M, Cc, OH, OW, mode) -> bool:
+    return _wgrad_tile(wgrad_query_desc(M, Cc, OH, OW, mode)) == (5 if mode == B_PLAIN else 4)
+
+
 def wgrad_bx3_eligible(M, Cc, OH, OW, mode) -> bool:
-    """Problems the split-precision weight-gradient kernel takes (vd_wgrad_desc.math = 1)."""
-    if mode == B_PLAIN:
-        return (OH * OW) % 8 == 0 and M >= 64 and Cc >= 64
-    if (mode == B_CONV3 and OW == 4 and OH == 4) or (mode in (B_CONV3, B_CONV3_UP) and OW >= 64 and OW % 32 == 0):
-        return M >= 64 and Cc >= 64      # 4x4: two images per K-step; wide images: 32-pixel row segments
-    if mode == B_CONV3_S2:                   # round 4: the Downsample2D convolution (stride 2) at 8x8 .. 32x32 outputs and 32-pixel segments of wider ones
-        return OH == OW and (OW in (8, 16, 32) or (OW >= 64 and OW % 32 == 0)) and M >= 64 and Cc >= 64 and _wgrad_s2_split(OW)
-    return mode in (B_CONV3, B_CONV3_UP) and OH == OW and OW in (8, 16, 32) and M >= 64 and Cc >= 64
+    """Problems the split-precision weight-gradient kernels take (vd_wgrad_desc.math = 1; tile 4 / 5 of vd_conv_wgrad_plan), less the stride-2 ones
+    VILLAN_WGRAD_S2 switches off."""
+    return _wgrad_split_kernel(M, Cc, OH, OW, mode) and (mode != B_CONV3_S2 or _wgrad_s2_split(OW))
 
 
 def wgrad_ws_floats(M, Cc, T, nb, NP, OH=None, OW=None, mode=None, math_mode=0) -> int:
     """Workspace floats vd_conv_wgrad needs (square outputs assumed when OH/OW are omitted)."""
-    d = WgradDesc()
     if OH is None:
         OH = OW = int(round(math.sqrt(NP)))
-    d.M, d.C, d.T, d.nb, d.NP, d.OH, d.OW = M, Cc, T, nb, NP, OH, OW
-    d.mode = (B_PLAIN if T == 1 else B_CONV3) if mode is None else mode
-    d.math = math_mode
-    scale = {B_CONV3_UP: (1, 2), B_CONV3_S2: (2, 1)}.get(d.mode, (1, 1))          # source dims of the gather
-    d.H, d.W = OH * scale[0] // scale[1], OW * scale[0] // scale[1]
+    d = wgrad_query_desc(M, Cc, OH, OW, (B_PLAIN if T == 1 else B_CONV3) if mode is None else mode, nb, math_mode, NP=NP)
     return int(L.load().vd_conv_wgrad_ws_floats(C.byref(d)))
 
 
