@@ -42,10 +42,12 @@ MODE_MEASURE_OPTS = MODE_SAMPLING_OPTS
 IGNORE_ARGS = {"overwrite", "is_save_all_model_epochs", "R_trigger_only"}
 # options of this build beyond the reference's: --ema_decay (train modes; resume takes it from args.json), --use_ema (sampling / measure),
 # --lora_r / --lora_alpha / --lora_target / --lora_backward (train modes: a LoRA fine-tune, villandiffusion_amd.lora; resume takes them from
-# args.json).
+# args.json), --snr_gamma / --poison_loss_weight / --log_loss_split (train modes: the shaped loss, villandiffusion_amd.loss.LossFn snr_gamma /
+# poison_weight / track_split; resume takes them from args.json).
 # At their defaults they are left out of the JSON side files, which then read as they did before the options existed.
 EXTRA_MODE_OPTS = {MODE_SAMPLING: {"use_ema"}, MODE_MEASURE: {"use_ema"}}
-EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False, "lora_r": None, "lora_alpha": None, "lora_target": "attn", "lora_backward": None}
+EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False, "lora_r": None, "lora_alpha": None, "lora_target": "attn", "lora_backward": None,
+                  "snr_gamma": None, "poison_loss_weight": 1.0, "log_loss_split": False}
 
 
 def _side_file(d: dict) -> dict:
@@ -85,6 +87,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     a("--lora_r", type=int); a("--lora_alpha", type=float); a("--lora_target", type=str, choices=["attn", "conv", "all"])
     # "adapted": the backward forms only the gradients the adapter needs (absent = "full": every weight gradient, as a full fine-tune does)
     a("--lora_backward", type=str, choices=["full", "adapted"])
+    # not in the reference: min-SNR-gamma weights by timestep, a weight on the poisoned samples' loss, and the clean / poisoned loss in the progress line
+    a("--snr_gamma", type=float); a("--poison_loss_weight", type=float); a("--log_loss_split", action="store_true")
     return p.parse_args(argv)
 
 
@@ -107,6 +111,7 @@ class TrainingConfig:
     clip: bool = False; output_dir: str = ""; ckpt_path: Optional[str] = None; data_ckpt_path: Optional[str] = None
     ema_decay: Optional[float] = None; use_ema: bool = False
     lora_r: Optional[int] = None; lora_alpha: Optional[float] = None; lora_target: str = "attn"; lora_backward: Optional[str] = None
+    snr_gamma: Optional[float] = None; poison_loss_weight: float = 1.0; log_loss_split: bool = False
     extra: dict = field(default_factory=dict)
 
 
@@ -146,6 +151,7 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
             setattr(cfg, k, v)
     cfg.mode = mode
     lora_config(cfg)                                                   # ValueError / NotImplementedError before anything is created
+    loss_shaping(cfg)
     cfg.clip = cfg.fclip == "w"                                        # :252-258
     # f32 tensors everywhere by default (reference :260-264: fp16 autocast + GradScaler for SDE-VP / SDE-LDM).  VILLAN_MIXED_PRECISION=fp16 opts
     # into the library's mixed-precision arithmetic (UNet2DModel.conv_math = "f16": single f16 products in the full-size convolutions, loss scaling);
@@ -215,6 +221,27 @@ def lora_config(cfg: TrainingConfig):
     if training and (len(str(cfg.gpu).split(",")) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         raise NotImplementedError("--lora_r on more than one GPU is not built")
     return lc
+
+
+def loss_shaping(cfg: TrainingConfig) -> dict:
+    """The LossFn keywords --snr_gamma / --poison_loss_weight / --log_loss_split ask for ({} at their defaults).  Raises what LossFn would
+    (a gamma or weight out of range, --snr_gamma with SDE-VE) before anything is created."""
+    from villandiffusion_amd.loss import check_shaping
+    check_shaping(cfg.snr_gamma, cfg.poison_loss_weight, cfg.sde_type)
+    kw = {}
+    if cfg.snr_gamma is not None:
+        kw["snr_gamma"] = float(cfg.snr_gamma)
+    if cfg.poison_loss_weight != 1.0:
+        kw["poison_weight"] = float(cfg.poison_loss_weight)
+    if cfg.log_loss_split:
+        kw["track_split"] = True
+    return kw
+
+
+def split_fields(acc) -> str:
+    """' loss_clean X loss_poison Y' from the accumulated [sum clean, n clean, sum poisoned, n poisoned]; n/a for a class without a sample."""
+    sc, nc, sp, n_p = (float(v) for v in acc)
+    return (f" loss_clean {sc / nc:.5f}" if nc > 0 else " loss_clean n/a") + (f" loss_poison {sp / n_p:.5f}" if n_p > 0 else " loss_poison n/a")
 
 
 # ----------------------------------------------------------------------------------------------------------------- run
@@ -498,7 +525,9 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
     if world > 1:                                                      # identical replicas
         torch.distributed.broadcast(model.flat_param, src=0)
     loss_fn = LossFn(noise_sched=noise_sched, sde_type=cfg.sde_type, loss_type="l2", psi=cfg.psi, solver_type=cfg.solver_type,
-                     vp_scale=cfg.vp_scale, ve_scale=cfg.ve_scale)
+                     vp_scale=cfg.vp_scale, ve_scale=cfg.ve_scale, **loss_shaping(cfg))
+    if loss_fn.shaped:
+        dsl.batch_flags = True                                         # the lean training batches carry `is_clean` for the shaped loss
     n_batch = (len(dsl) + cfg.batch * world - 1) // (cfg.batch * world)
     trainer = Trainer(model, loss_fn, lr=cfg.learning_rate, total_steps=n_batch * cfg.epoch, warmup_steps=cfg.lr_warmup_steps,
                       grad_accum=cfg.gradient_accumulation_steps, ema=EMAConfig(decay=cfg.ema_decay) if cfg.ema_decay is not None else None,
@@ -517,6 +546,7 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
         sampling(cfg, 0, pipeline, dsl)
     T = noise_sched.config.num_train_timesteps
     epoch = start_epoch
+    split_acc = torch.zeros(4, device=model.device) if cfg.log_loss_split else None      # summed on the device, read where a line is printed
     for epoch in range(start_epoch, cfg.epoch):
         loader = dsl.get_dataloader(rank=rank, world=world, epoch=epoch, full=False)
         nb = len(loader)
@@ -525,8 +555,14 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
             t = torch.randint(0, T, (bs,), device=model.device).long()            # reference :1151
             loss = trainer.train_step(batch, t, last_batch=(i == nb - 1), target_key=TARGET_LATENT_KEY)
             step += 1
+            if split_acc is not None and loss_fn.last_split is not None:
+                split_acc += loss_fn.last_split
             if rank == 0 and (step % 50 == 0 or i == nb - 1):
-                print(f"epoch {epoch} step {step} loss {float(loss):.5f} lr {trainer.lr:.3e}", flush=True)
+                split = ""
+                if split_acc is not None:
+                    split = split_fields(split_acc.tolist())
+                    split_acc.zero_()
+                print(f"epoch {epoch} step {step} loss {float(loss):.5f} lr {trainer.lr:.3e}{split}", flush=True)
         if rank == 0:
             if (epoch + 1) % cfg.save_image_epochs == 0 or epoch == cfg.epoch - 1:
                 with sampling_weights():

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VD_ABI_VERSION 12 /* 12: vd_gemm_kernel_name / vd_conv_wgrad_kernel_name / vd_conv_wgrad_group_kernel_name; a refused pool2 problem answers -1 at vd_gemm_tile.  Unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step / vd_lora_merge / vd_lora_grad / vd_lora_act_grad / vd_lora_act_grad_ws_floats: additions only */
+#define VD_ABI_VERSION 12 /* 12: vd_gemm_kernel_name / vd_conv_wgrad_kernel_name / vd_conv_wgrad_group_kernel_name; a refused pool2 problem answers -1 at vd_gemm_tile.  Unchanged by vd_removal_loss / vd_image_set_stats / vd_score_inv_objective / vd_pyramid_dgrad / vd_image_set_merge / vd_adam_ema_step / vd_swap / vd_neuron_scale / vd_neuron_grad / vd_neuron_step / vd_lora_merge / vd_lora_grad / vd_lora_act_grad / vd_lora_act_grad_ws_floats / vd_loss_sample_fwd_bwd / vd_loss_sample_ws_floats / vd_loss_sample_plan: additions only */
 #define VD_EINVAL (-22)
 #define VD_ETIMEDOUT (-110) /* an EARLIER asynchronous launch reported a bounded-poll timeout (see vd_async_errors) */
 
@@ -406,6 +406,23 @@ int vd_mse_fwd_bwd(const float* pred, const float* y, const float* pscale, float
 #define VD_LOSS_HUBER 2
 int vd_loss_fwd_bwd(const float* pred, const float* y, const float* pscale, float* dpred, float* loss,
                     float* partial, int B, int64_t chw, float gscale, int kind, void* stream);
+/* The shaped loss: vd_loss_fwd_bwd with a weight per sample in and the loss of every sample out.  With d = pred[b,i] * ps_b - y[b,i] and norm /
+ * norm' those of vd_loss_fwd_bwd:
+ *   l[b]  = (1/chw) sum_i norm(d)                                              (sample_loss, UNWEIGHTED)
+ *   w[b]  = (weight ? weight[b] : 1) * (wtab ? wtab[clamp(t[b], 0, T-1)] : 1) * (flags && flags[b] ? poison_weight : 1)
+ *   *loss = (1/B) sum_b w[b] l[b]                                              (the mean of the weighted sample losses, not divided by sum w)
+ *   dpred[b,i] = ((gcoef * w[b]) * norm'(d)) * ps_b,  gcoef = (kind == VD_LOSS_L2 ? 2 : 1) * gscale / (B * chw)
+ *   stats = {sum of l[b] over the clean samples, their count, sum of l[b] over the poisoned (flags[b] != 0) ones, their count}
+ * With every weight 1 dpred has the bits vd_loss_fwd_bwd writes.  pscale, weight, flags: [B] or NULL; wtab: [T] or NULL (then t may be NULL);
+ * dpred NULL: forward only; sample_loss [B] and stats [4] may be NULL; ws: vd_loss_sample_ws_floats(B, chw) floats.  Every sample is cut into
+ * `segments` pieces, each summed by one 256-thread workgroup (16-byte loads when chw % 4 == 0 and pred, y, dpred are 16-byte aligned), and one
+ * last workgroup adds the pieces in index order: no atomics, the same bits in every run.  vd_loss_sample_plan (host only) answers the segment
+ * count and the grid the launcher uses for (B, chw). */
+int vd_loss_sample_fwd_bwd(const float* pred, const float* y, const float* pscale, const float* weight, const float* wtab, const int64_t* t,
+                           int T, const uint8_t* flags, float poison_weight, float* dpred, float* loss, float* sample_loss, float* stats,
+                           float* ws, int B, int64_t chw, float gscale, int kind, void* stream);
+int64_t vd_loss_sample_ws_floats(int B, int64_t chw);
+int vd_loss_sample_plan(int B, int64_t chw, int* segments, int* blocks);
 /* Trigger-inversion objective (distribution shift, Elijah): r = mean_b e[b] - lambda * tau, *loss = L = ||r||_2 over the chw elements,
  * dout[b] = r / (B L) for every b (the gradient of L with respect to e, contiguous [B, chw]) and dtau = -lambda r / L (the direct term of
  * dL/dtau; the term through the network is the sum over b of the network's input gradient).  e: [B, chw] with batch stride e_bstride >= chw;

@@ -377,6 +377,7 @@ class DatasetLoader:
         self._dev_images = None
         self._R_trigger_only = False
         self.random_flip = True            # dataset.py:165-168: RandomHorizontalFlip is always on
+        self.batch_flags = False           # True: training batches (full=False) carry `is_clean` too (a shaped loss reads it; one more small launch)
 
     # ---- reference surface ----
     def set_poison(self, trigger_type: str, target_type: str, target_dx: int = -5, target_dy: int = -3, clean_rate: float = 1.0,
@@ -500,8 +501,9 @@ class DatasetLoader:
         if poi.shape[0] > 0:
             pv = torch.where(m, poi[idx.clamp(max=poi.shape[0] - 1)], pv)
         batch = {self.PIXEL_VALUES: pv.contiguous(), self.TARGET: torch.where(m, tgt[None].expand_as(r), r).contiguous(), self.IMAGE: r}
-        if full:
+        if full or self.batch_flags:
             batch[self.IS_CLEAN] = ~is_p
+        if full:
             batch[self.LABEL] = torch.full((len(idx),), -1.0, device=self._dev)
         return batch
 
@@ -622,6 +624,8 @@ class DatasetLoader:
             lab = torch.full((B,), -1.0) if self._labels is None else torch.from_numpy(self._labels[self._index[pos]]).float()
             batch[self.LABEL] = self._h2d(lab)
             batch[self.IS_CLEAN] = ~is_p
+        elif self.batch_flags:
+            batch[self.IS_CLEAN] = ~self._h2d((flags & 1).bool())
         return batch
 
     def _make_batch_resident(self, pos: torch.Tensor, flip_bits: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -642,7 +646,10 @@ class DatasetLoader:
         pv, tg, im = (torch.empty((B, C, S, S), device=self._dev, dtype=torch.float32) for _ in range(3))
         ops.poison_batch(self._dev_images, kflags.contiguous(), self._dev_trigger, self._dev_target, pv, tg, im, self._vmin, self._vmax,
                          R_trigger_only=False, idx=ds_idx)
-        return {self.PIXEL_VALUES: pv, self.TARGET: tg, self.IMAGE: im}
+        batch = {self.PIXEL_VALUES: pv, self.TARGET: tg, self.IMAGE: im}
+        if self.batch_flags:
+            batch[self.IS_CLEAN] = (fl & 1) == 0
+        return batch
 
     def get_dataloader(self, batch_size: int = None, shuffle: bool = None, num_workers: int = None, collate_fn=None,
                        rank: int = 0, world: int = 1, epoch: int = 0, full: bool = True):

@@ -102,6 +102,9 @@ PROTOTYPES = {
     "vd_qsample_backdoor": (_i32, [_vp] * 10 + [_i32, _i64, _vp]),
     "vd_mse_fwd_bwd": (_i32, [_vp] * 6 + [_i32, _i64, _f32, _vp]),
     "vd_loss_fwd_bwd": (_i32, [_vp] * 6 + [_i32, _i64, _f32, _i32, _vp]),
+    "vd_loss_sample_fwd_bwd": (_i32, [_vp] * 6 + [_i32, _vp, _f32] + [_vp] * 5 + [_i32, _i64, _f32, _i32, _vp]),
+    "vd_loss_sample_ws_floats": (_i64, [_i32, _i64]),
+    "vd_loss_sample_plan": (_i32, [_i32, _i64, C.POINTER(_i32), C.POINTER(_i32)]),
     "vd_trigger_inv_objective": (_i32, [_vp, _vp, _f32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     "vd_removal_loss": (_i32, [_vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     "vd_score_inv_objective": (_i32, [_vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),

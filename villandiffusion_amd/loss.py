@@ -5,10 +5,13 @@ What changed under the surface
 * the (step, coef) correction tables (L1-L3 in SURVEY.md §8a) are built ONCE on the host with the reference's fp32 op
   sequence and kept on the device (the reference rebuilds them every step, loss.py:917);
 * q-sample + backdoor shift + target (L4) is ONE kernel (``vd_qsample_backdoor``) and MSE forward+backward (L5)
-  is ONE kernel pair (``vd_mse_fwd_bwd``); ``loss.backward()`` then drives the UNet's explicit backward.
+  is ONE kernel pair (``vd_mse_fwd_bwd``); ``loss.backward()`` then drives the UNet's explicit backward;
+* a *shaped* loss (``snr_gamma`` / ``poison_weight`` / ``track_split``, all off by default) runs ``vd_loss_sample_fwd_bwd`` in its place: a
+  weight per sample in, the loss of every sample and the clean / poisoned split out, still one fused gradient.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Tuple
 
 import torch
@@ -88,6 +91,26 @@ def get_R_coef_gen_ve_reduce(sigmas, hs=None, rhos_hat_w: float = 1.0, psi: floa
     return _solver(rhos_hat_w * sigmas, ve_scale * (sigmas * rhos_hat_w / (sigmas + prev)), solver_type)
 
 
+# ---------------------------------------------------------------------------------------------- min-SNR weights
+def min_snr_table(alphas_cumprod: torch.Tensor, gamma: float) -> torch.Tensor:
+    """Min-SNR-gamma weights of an epsilon-prediction loss, one per timestep: snr = abar / (1 - abar), w = min(snr, gamma) / snr, in float32
+    torch ops on the host.  Exactly 1 wherever snr <= gamma (x / x), below 1 at the low-noise timesteps."""
+    ac = alphas_cumprod.detach().float().cpu()
+    snr = ac / (1 - ac)
+    return torch.minimum(snr, torch.tensor(float(gamma), dtype=torch.float32)) / snr
+
+
+def check_shaping(snr_gamma, poison_weight, sde_type=None):
+    """The argument errors of the shaped loss, raised before any launch."""
+    if snr_gamma is not None:
+        if sde_type == SDE_VE:
+            raise NotImplementedError("snr_gamma with SDE-VE isn't implemented: the VE loss already carries its own sigma weighting")
+        if not (isinstance(snr_gamma, (int, float)) and math.isfinite(snr_gamma) and snr_gamma > 0):
+            raise ValueError(f"snr_gamma must be a finite number > 0, got {snr_gamma!r}")
+    if not (isinstance(poison_weight, (int, float)) and math.isfinite(poison_weight) and poison_weight >= 0):
+        raise ValueError(f"poison_weight must be a finite number >= 0, got {poison_weight!r}")
+
+
 # ---------------------------------------------------------------------------------------------- fused MSE
 class _MSE(torch.autograd.Function):
     @staticmethod
@@ -104,16 +127,43 @@ class _MSE(torch.autograd.Function):
         return dpred * g, None, None, None, None, None
 
 
+class _ShapedLoss(torch.autograd.Function):
+    """_MSE for a shaped LossFn: the same one-pass forward + gradient through vd_loss_sample_fwd_bwd."""
+
+    @staticmethod
+    def forward(ctx, pred, y, pscale, lf, timesteps, flags, weight):
+        dpred = torch.empty_like(pred)
+        loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+        lf.shaped_launch(pred.contiguous(), y, dpred, loss, pscale, timesteps, flags, weight)
+        ctx.save_for_backward(dpred)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return dpred * g, None, None, None, None, None, None
+
+
 class LossFn:
     """Drop-in for the reference's ``LossFn`` (same constructor and ``p_loss`` / ``p_loss_by_keys`` signatures)."""
     RANDN_BOUND: float = 2.5
 
     def __init__(self, noise_sched, sde_type: str, loss_type: str = "l2", psi: float = 1, solver_type: str = "sde",
-                 vp_scale: float = 1.0, ve_scale: float = 1.0, rhos_hat_w: float = 1.0, rhos_hat_b: float = 0.0):
+                 vp_scale: float = 1.0, ve_scale: float = 1.0, rhos_hat_w: float = 1.0, rhos_hat_b: float = 0.0,
+                 snr_gamma: Optional[float] = None, poison_weight: float = 1.0, track_split: bool = False):
+        """snr_gamma / poison_weight / track_split (after the reference's arguments) shape the loss: min-SNR-gamma weights by timestep
+        (VP / LDM), a weight on the poisoned samples, and the clean / poisoned split kept in ``last_split``.  All at their defaults: the loss
+        of the reference, through the kernels it always ran."""
         if sde_type not in (SDE_VP, SDE_VE, SDE_LDM):
             raise NotImplementedError(f"sde_type: {sde_type} isn't implemented")
         if loss_type not in ops.LOSS_KINDS:       # loss.py:849-858: l1 / l2 / huber, anything else raises
             raise NotImplementedError(f"loss_type: {loss_type} isn't implemented")
+        check_shaping(snr_gamma, poison_weight, sde_type)
+        self.snr_gamma, self.poison_weight, self.track_split = snr_gamma, poison_weight, bool(track_split)
+        self.last_sample_loss: Optional[torch.Tensor] = None      # [B] unweighted per-sample losses of the last shaped call (device, no sync)
+        self.last_split: Optional[torch.Tensor] = None            # [4] {sum l clean, n clean, sum l poisoned, n poisoned} of it
+        self._wtab = None                                         # (gamma, {device: table})
+        self._ws = None
         self._loss_type = loss_type
         self._sched, self._sde, self._psi, self._solver = noise_sched, sde_type, psi, solver_type
         # the schedule is captured HERE like the reference does (loss.py:829-834): a VE pipeline's set_sigmas(n) later
@@ -153,6 +203,59 @@ class LossFn:
             self._partial = torch.empty(1024, device=dev, dtype=torch.float32)
         return self._dev_tabs
 
+    # ---- shaping -----------------------------------------------------------------------------------------------------------------
+    @property
+    def shaping(self) -> Tuple:
+        """(snr_gamma, poison_weight, track_split): what a captured micro-step was recorded with."""
+        return (self.snr_gamma, self.poison_weight, self.track_split)
+
+    @property
+    def shaped(self) -> bool:
+        return self.snr_gamma is not None or self.poison_weight != 1.0 or self.track_split
+
+    def snr_table(self, dev=None) -> Optional[torch.Tensor]:
+        """The min-SNR-gamma table [T] (None without snr_gamma): built once per gamma on the host, kept on `dev` beside the other tables."""
+        if self.snr_gamma is None:
+            return None
+        check_shaping(self.snr_gamma, self.poison_weight, self._sde)
+        dev = torch.device("cpu") if dev is None else torch.device(dev)
+        if self._wtab is None or self._wtab[0] != self.snr_gamma:
+            self._wtab = (self.snr_gamma, {})
+        tabs = self._wtab[1]                          # one per device, never replaced: a captured micro-step holds the device one's address
+        if dev not in tabs:
+            tabs[dev] = min_snr_table(self._alphas_cumprod, self.snr_gamma).to(dev).contiguous()
+        return tabs[dev]
+
+    def shaped_flags(self, is_poison, Bn: int, dev) -> Optional[torch.Tensor]:
+        """The poison flags [B] as device bytes; a poison weight or the split without them is an error (raised before any launch)."""
+        check_shaping(self.snr_gamma, self.poison_weight, self._sde)
+        if is_poison is None:
+            if self.poison_weight != 1.0 or self.track_split:
+                raise ValueError("LossFn: poison_weight != 1 or track_split needs the poison flags (is_poison=..., or batch['is_clean'])")
+            return None
+        flags = torch.as_tensor(is_poison)
+        if flags.numel() != Bn:
+            raise ValueError(f"LossFn: is_poison has {flags.numel()} entries for a batch of {Bn}")
+        return (flags != 0).reshape(Bn).to(dev).contiguous()
+
+    def shaped_launch(self, pred, y, dpred, loss, pscale, timesteps, flags, weight=None, ws=None):
+        """One vd_loss_sample_fwd_bwd launch with this LossFn's shaping (dpred None: forward only); leaves last_sample_loss / last_split."""
+        dev, Bn = pred.device, pred.shape[0]
+        if ws is None:
+            need = ops.loss_sample_plan(Bn, pred.numel() // Bn)[2]
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
+                self._ws = torch.empty(need, device=dev, dtype=torch.float32)
+            ws = self._ws
+        wtab = self.snr_table(dev)
+        sample_loss = torch.empty(Bn, device=dev, dtype=torch.float32)
+        stats = torch.empty(4, device=dev, dtype=torch.float32)
+        ops.loss_sample_fwd_bwd(pred, y, dpred, loss, ws, pscale=pscale, weight=weight, wtab=wtab,
+                                t=timesteps.to(device=dev, dtype=torch.int64).contiguous() if wtab is not None else None, flags=flags,
+                                poison_weight=self.poison_weight, sample_loss=sample_loss, stats=stats, gscale=self.grad_scale,
+                                kind=self._loss_type)
+        self.last_sample_loss, self.last_split = sample_loss, stats
+        return loss
+
     def get_inputs_targets(self, x_start, R, timesteps, noise):
         """(x_t, y) of loss.py:909-939 in one kernel."""
         dev = x_start.device
@@ -170,10 +273,20 @@ class LossFn:
         self._noise_off += (x.numel() + 3) // 4
         return z
 
-    def p_loss(self, model, x_start: torch.Tensor, R: torch.Tensor, timesteps: torch.Tensor, noise: torch.Tensor = None):
+    def p_loss(self, model, x_start: torch.Tensor, R: torch.Tensor, timesteps: torch.Tensor, noise: torch.Tensor = None,
+               is_poison: Optional[torch.Tensor] = None, sample_weight: Optional[torch.Tensor] = None):
+        """is_poison [B] (bool): the samples poison_weight and the split apply to; sample_weight [B]: an explicit weight per sample.  Either
+        one makes this call a shaped one."""
         if len(x_start) == 0:
             return 0
         dev = model.device if hasattr(model, "device") else x_start.device
+        shaped = self.shaped or sample_weight is not None
+        if shaped:                                    # every argument error before the first launch
+            flags = self.shaped_flags(is_poison, len(x_start), dev)
+            if sample_weight is not None:
+                if sample_weight.numel() != len(x_start):
+                    raise ValueError(f"LossFn: sample_weight has {sample_weight.numel()} entries for a batch of {len(x_start)}")
+                sample_weight = sample_weight.to(dev).float().reshape(-1).contiguous()
         x_start, R = x_start.to(dev).float(), R.to(dev).float()
         timesteps = timesteps.to(dev)
         if noise is None:
@@ -181,9 +294,13 @@ class LossFn:
         x_t, y = self.get_inputs_targets(x_start, R, timesteps, noise.to(dev))
         if self._sde in (SDE_VP, SDE_LDM):
             pred = model(x_t, timesteps.contiguous(), return_dict=False)[0]
+            if shaped:
+                return _ShapedLoss.apply(pred, y, None, self, timesteps, flags, sample_weight)
             return _MSE.apply(pred, y, None, self.grad_scale, self._partial, self._loss_type)
         sig_t = self._dev_tabs[3][timesteps]
         pred = model(x_t, sig_t.contiguous(), return_dict=False)[0]
+        if shaped:
+            return _ShapedLoss.apply(pred, y, (-sig_t).contiguous(), self, timesteps, flags, sample_weight)
         return _MSE.apply(pred, y, (-sig_t).contiguous(), self.grad_scale, self._partial, self._loss_type)
 
     def p_loss_by_keys(self, batch, model, target_latent_key, poison_latent_key, timesteps, vae=None, noise=None,
@@ -191,7 +308,10 @@ class LossFn:
         x0, R = batch[target_latent_key], batch[poison_latent_key]
         if vae is not None:          # loss.py:942-970: encode on the fly (training itself passes vae=None + precomputed latents)
             x0, R = self.encode_latents(vae, x0, scaling_factor), self.encode_latents(vae, R, scaling_factor)
-        return self.p_loss(model=model, x_start=x0, R=R, timesteps=timesteps, noise=noise)
+        is_poison = None
+        if self.shaped and "is_clean" in batch:      # (an unshaped loss never looks at the flags: not one more launch)
+            is_poison = ~torch.as_tensor(batch["is_clean"]).bool()
+        return self.p_loss(model=model, x_start=x0, R=R, timesteps=timesteps, noise=noise, is_poison=is_poison)
 
     @staticmethod
     def encode_latents(vae, x: torch.Tensor, scaling_factor: Optional[float] = None) -> torch.Tensor:

@@ -1040,6 +1040,43 @@ def mse_fwd_bwd(pred, y, dpred, loss, partial, pscale=None, gscale=1.0, kind="l2
     return loss
 
 
+def loss_sample_plan(Bn: int, chw: int):
+    """(segments, blocks, workspace floats) vd_loss_sample_fwd_bwd uses for [Bn, chw]: asked of the library on the host, no device needed."""
+    seg, blk = C.c_int32(0), C.c_int32(0)
+    lib = L.load()
+    L.check(lib.vd_loss_sample_plan(int(Bn), int(chw), C.byref(seg), C.byref(blk)), "vd_loss_sample_plan")
+    return seg.value, blk.value, int(lib.vd_loss_sample_ws_floats(int(Bn), int(chw)))
+
+
+def loss_sample_fwd_bwd(pred, y, dpred, loss, ws, *, pscale=None, weight=None, wtab=None, t=None, flags=None, poison_weight=1.0,
+                        sample_loss=None, stats=None, gscale=1.0, kind="l2"):
+    """The shaped loss (vd_loss_sample_fwd_bwd): loss = mean_b w[b] l[b] with l[b] = mean_i norm(pred[b] * pscale[b] - y[b]) and
+    w[b] = weight[b] * wtab[clamp(t[b])] * (poison_weight where flags[b]), absent factors 1; dpred (None: forward only) its gradient times
+    gscale; sample_loss [B] the unweighted l[b]; stats [4] = {sum l over clean, n clean, sum l over poisoned, n poisoned}.  flags: bool or
+    uint8 [B].  ws: at least loss_sample_plan(B, chw)[2] floats.  Bit-reproducible; all weights 1 gives mse_fwd_bwd's dpred bits."""
+    Bn = pred.shape[0]
+    chw = pred.numel() // Bn
+    assert pred.is_contiguous() and y.is_contiguous() and pred.dtype == y.dtype == torch.float32 and y.numel() == pred.numel()
+    assert dpred is None or (dpred.is_contiguous() and dpred.dtype == torch.float32 and dpred.numel() == pred.numel())
+    for v in (pscale, weight, sample_loss):
+        assert v is None or (v.is_contiguous() and v.dtype == torch.float32 and v.numel() == Bn)
+    assert stats is None or (stats.is_contiguous() and stats.dtype == torch.float32 and stats.numel() == 4)
+    assert loss.dtype == torch.float32 and loss.numel() >= 1
+    Tn = 0
+    if wtab is not None:
+        assert wtab.is_contiguous() and wtab.dtype == torch.float32 and wtab.numel() > 0
+        assert t is not None and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == Bn
+        Tn = wtab.numel()
+    if flags is not None:
+        assert flags.dtype in (torch.bool, torch.uint8) and flags.is_contiguous() and flags.numel() == Bn      # one byte each, nonzero: poisoned
+    assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.numel() >= L.load().vd_loss_sample_ws_floats(Bn, chw)
+    _timed("loss_sample_fwd_bwd (loss_sample_kernel + loss_sample_finish_kernel)", 4.0 * (2 if dpred is None else 3) * Bn * chw, "hbm", lambda: L.check(
+        _lib().vd_loss_sample_fwd_bwd(_p(pred), _p(y), _p(pscale), _p(weight), _p(wtab), _p(t if wtab is not None else None), Tn, _p(flags),
+                                      float(poison_weight), _p(dpred), _p(loss), _p(sample_loss), _p(stats), _p(ws), Bn, chw, gscale,
+                                      LOSS_KINDS[kind], _s()), "vd_loss_sample_fwd_bwd"))
+    return loss
+
+
 def trigger_inv_objective(e, tau, lam, loss, dout, dtau, partial):
     """loss = || mean_b e[b] - lam * tau ||_2, dout[b] = dloss/de[b] (every b) and dtau = the direct term -lam * r / loss, in one call
     (vd_trigger_inv_objective: fixed-order two-phase sum, bit-reproducible; loss == 0 gives zero gradients)."""

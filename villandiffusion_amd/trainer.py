@@ -153,10 +153,11 @@ class GraphedMicroStep:
     and replayed (BASELINE config #1: `--batch 4` with gradient accumulation 32, VillanDiffusion.py:287 -- a micro-step is ~470 launches of
     5-20 us kernels, so eager launch is host-bound: the GPU idles between them).  The graph calls the network's explicit launch sequences
     directly (no autograd tape inside the capture), accumulates into the flat gradient buffer like `loss.backward()` does and leaves the
-    un-divided micro-batch loss in `self.loss`.  Static inputs: clean image, poison residual, noise, timesteps.  Single-process VP / LDM
+    un-divided micro-batch loss in `self.loss`.  Static inputs: clean image, poison residual, noise, timesteps, and the poison flags of a shaped
+    loss (LossFn snr_gamma / poison_weight / track_split: the shaped loss kernel is what the capture holds then).  Single-process VP / LDM
     training only (the bucketed all-reduce hooks of a multi-rank step fire from inside the backward pass and are not captured)."""
 
-    def __init__(self, trainer, x0, R, noise, t):
+    def __init__(self, trainer, x0, R, noise, t, flags=None):
         import torch.cuda
         net, lf = trainer.model, trainer.loss_fn
         self.trainer, self.net = trainer, net
@@ -168,6 +169,10 @@ class GraphedMicroStep:
         self.key = self._key()
         for buf, v in ((self.x0, x0), (self.R, R), (self.noise, noise), (self.t, t)):
             buf.copy_(v)
+        self.flags = self.ws = None
+        if getattr(lf, "shaped", False):                  # the shaped loss: static flags, and a workspace of this graph's own (its address is captured)
+            self.flags = None if flags is None else flags.clone()
+            self.ws = torch.empty(ops.loss_sample_plan(x0.shape[0], x0[0].numel())[2], device=dev, dtype=torch.float32)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         keep = net.flat_grad.clone()
@@ -193,6 +198,7 @@ class GraphedMicroStep:
                 self._body()
         finally:
             self._tables = ops.capture_end()              # device job tables the captured launches read: owned by this graph from now on
+        self._last = (lf.last_sample_loss, lf.last_split) if self.ws is not None else None      # the capture's own outputs: every replay refills them
         if _DEBUG:
             torch.cuda.synchronize(dev)
             print(f"[graph] captured; {len(self._tables)} job tables", flush=True)
@@ -201,7 +207,7 @@ class GraphedMicroStep:
         n = self.net
         route = getattr(n, "lora_route", None)
         return (n.conv_math, n.wgrad_stream, n.group_wgrad, n.flat_param.data_ptr(), n.flat_grad.data_ptr(), self.trainer.loss_fn.grad_scale,
-                None if route is None else (id(route), route.gab.data_ptr()))
+                None if route is None else (id(route), route.gab.data_ptr()), getattr(self.trainer.loss_fn, "shaping", None))
 
     def valid(self) -> bool:
         dev = self.net.device
@@ -215,10 +221,13 @@ class GraphedMicroStep:
         self.tf.copy_(self.t)                             # int64 -> float32 timesteps, as UNet2DModel.forward does
         pred, st = net._run_forward(x_t, self.tf, save=True)
         dpred = torch.empty_like(pred)
-        ops.mse_fwd_bwd(pred, y, dpred, self.loss, lf._partial, pscale=None, gscale=lf.grad_scale, kind=lf._loss_type)
+        if self.ws is not None:
+            lf.shaped_launch(pred, y, dpred, self.loss, None, self.t, self.flags, ws=self.ws)
+        else:
+            ops.mse_fwd_bwd(pred, y, dpred, self.loss, lf._partial, pscale=None, gscale=lf.grad_scale, kind=lf._loss_type)
         net._run_backward(st, dpred)
 
-    def __call__(self, x0, R, noise, t):
+    def __call__(self, x0, R, noise, t, flags=None):
         net = self.net
         if hasattr(net, "refresh_packed"):                # weights changed since the last replay: rebuild the packed operands (one launch each)
             net.refresh_packed(False)
@@ -230,7 +239,11 @@ class GraphedMicroStep:
         self.R.copy_(R)
         self.noise.copy_(noise)
         self.t.copy_(t)
+        if self.flags is not None:
+            self.flags.copy_(flags)
         self.graph.replay()
+        if self._last is not None:                        # (overwritten by the next replay, like self.loss)
+            self.trainer.loss_fn.last_sample_loss, self.trainer.loss_fn.last_split = self._last
         if _DEBUG:
             torch.cuda.synchronize(net.device)
             print("[graph] replayed", flush=True)
@@ -423,16 +436,19 @@ class Trainer:
         if len(x0) == 0 or getattr(m, "device", torch.device("cpu")).type != "cuda" or not hasattr(m, "_packed"):
             return None
         dev = m.device
+        flags = None
+        if getattr(lf, "shaped", False):                  # a shaped loss: its poison flags ride in the batch; missing ones raise here, before any launch
+            flags = lf.shaped_flags(~torch.as_tensor(batch["is_clean"]).bool() if "is_clean" in batch else None, len(x0), dev)
         x0, R = x0.to(dev).float(), R.to(dev).float()
         if noise is None:
             noise = lf._noise(x0)
         lf._tables(dev)
-        key = (tuple(x0.shape),)
+        key = (tuple(x0.shape), flags is not None)
         g = self._graphs.get(key)
         if g is None or not g.valid():
             self._graphs.clear()                          # one shape at a time: a graph's private pool pins the activations of a whole step
-            g = self._graphs[key] = GraphedMicroStep(self, x0, R, noise.to(dev), timesteps.to(dev))
-        return g(x0, R, noise.to(dev), timesteps.to(dev))
+            g = self._graphs[key] = GraphedMicroStep(self, x0, R, noise.to(dev), timesteps.to(dev), flags)
+        return g(x0, R, noise.to(dev), timesteps.to(dev), flags)
 
     def state_dict(self) -> Dict:
         if self._ema_swapped:
