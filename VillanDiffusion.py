@@ -43,11 +43,13 @@ IGNORE_ARGS = {"overwrite", "is_save_all_model_epochs", "R_trigger_only"}
 # options of this build beyond the reference's: --ema_decay (train modes; resume takes it from args.json), --use_ema (sampling / measure),
 # --lora_r / --lora_alpha / --lora_target / --lora_backward (train modes: a LoRA fine-tune, villandiffusion_amd.lora; resume takes them from
 # args.json), --snr_gamma / --poison_loss_weight / --log_loss_split (train modes: the shaped loss, villandiffusion_amd.loss.LossFn snr_gamma /
-# poison_weight / track_split; resume takes them from args.json).
+# poison_weight / track_split; resume takes them from args.json), --sam_rho / --sam_mode / --sam_eta / --sam_layers (train modes: sharpness-aware
+# steps, villandiffusion_amd.trainer.SAMConfig; resume takes them from args.json).
 # At their defaults they are left out of the JSON side files, which then read as they did before the options existed.
 EXTRA_MODE_OPTS = {MODE_SAMPLING: {"use_ema"}, MODE_MEASURE: {"use_ema"}}
 EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False, "lora_r": None, "lora_alpha": None, "lora_target": "attn", "lora_backward": None,
-                  "snr_gamma": None, "poison_loss_weight": 1.0, "log_loss_split": False}
+                  "snr_gamma": None, "poison_loss_weight": 1.0, "log_loss_split": False,
+                  "sam_rho": None, "sam_mode": None, "sam_eta": None, "sam_layers": None}
 
 
 def _side_file(d: dict) -> dict:
@@ -89,6 +91,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     a("--lora_backward", type=str, choices=["full", "adapted"])
     # not in the reference: min-SNR-gamma weights by timestep, a weight on the poisoned samples' loss, and the clean / poisoned loss in the progress line
     a("--snr_gamma", type=float); a("--poison_loss_weight", type=float); a("--log_loss_split", action="store_true")
+    # not in the reference: sharpness-aware steps (SAM / ASAM / neuron-adaptive): the gradient of every optimiser step is taken at perturbed weights
+    a("--sam_rho", type=float); a("--sam_mode", type=str, choices=["sam", "asam", "neuron"]); a("--sam_eta", type=float)
+    a("--sam_layers", type=str, choices=["conv", "all"])
     return p.parse_args(argv)
 
 
@@ -112,6 +117,7 @@ class TrainingConfig:
     ema_decay: Optional[float] = None; use_ema: bool = False
     lora_r: Optional[int] = None; lora_alpha: Optional[float] = None; lora_target: str = "attn"; lora_backward: Optional[str] = None
     snr_gamma: Optional[float] = None; poison_loss_weight: float = 1.0; log_loss_split: bool = False
+    sam_rho: Optional[float] = None; sam_mode: Optional[str] = None; sam_eta: Optional[float] = None; sam_layers: Optional[str] = None
     extra: dict = field(default_factory=dict)
 
 
@@ -176,6 +182,7 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
     if bs < cfg.batch:
         raise ValueError(f"batch size {cfg.batch} should be smaller or equal to {bs} for dataset {cfg.dataset}")
     cfg.gradient_accumulation_steps = int(bs // cfg.batch)
+    sam_config(cfg)                                                    # ValueError / NotImplementedError before anything is created
     # One process per GPU (torchrun): every rank computes the same config, but the existing-directory check, the directory
     # creation and the JSON side files belong to rank 0 alone -- main() puts a barrier behind it.  (The reference is a single
     # process driving nn.DataParallel, :440, so it has no such distinction.)
@@ -221,6 +228,26 @@ def lora_config(cfg: TrainingConfig):
     if training and (len(str(cfg.gpu).split(",")) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         raise NotImplementedError("--lora_r on more than one GPU is not built")
     return lc
+
+
+def sam_config(cfg: TrainingConfig):
+    """The SAMConfig --sam_rho / --sam_mode / --sam_eta / --sam_layers ask for, or None.  In the train modes it raises what Trainer would for
+    the combinations SAM is not built for (gradient accumulation, LoRA, more than one GPU, the f16 mode), before a device is touched."""
+    if cfg.sam_rho is None:
+        if cfg.sam_mode is not None or cfg.sam_eta is not None or cfg.sam_layers is not None:
+            raise ValueError("--sam_mode / --sam_eta / --sam_layers need --sam_rho")
+        return None
+    from villandiffusion_amd.trainer import SAMConfig, check_sam
+    kw = {k: v for k, v in (("mode", cfg.sam_mode), ("eta", cfg.sam_eta), ("layers", cfg.sam_layers)) if v is not None}
+    sc = SAMConfig(rho=cfg.sam_rho, **kw)                              # ValueError for a rho that is not positive, a negative eta, ...
+    if cfg.mode in (MODE_TRAIN, MODE_RESUME, MODE_TRAIN_MEASURE):
+        world = max(len(str(cfg.gpu).split(",")), int(os.environ.get("WORLD_SIZE", "1")))
+        if cfg.gradient_accumulation_steps > 1:
+            raise ValueError(f"--sam_rho needs an effective gradient-accumulation count of 1, got {cfg.gradient_accumulation_steps} "
+                             f"(the data set's batch size over --batch {cfg.batch}): SAM under gradient accumulation is not built")
+        check_sam(sc, cfg.gradient_accumulation_steps, lora=cfg.lora_r, world=world,
+                  conv_math="f16" if getattr(cfg, "mixed_precision", "no") == "fp16" else None)
+    return sc
 
 
 def loss_shaping(cfg: TrainingConfig) -> dict:
@@ -531,7 +558,7 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
     n_batch = (len(dsl) + cfg.batch * world - 1) // (cfg.batch * world)
     trainer = Trainer(model, loss_fn, lr=cfg.learning_rate, total_steps=n_batch * cfg.epoch, warmup_steps=cfg.lr_warmup_steps,
                       grad_accum=cfg.gradient_accumulation_steps, ema=EMAConfig(decay=cfg.ema_decay) if cfg.ema_decay is not None else None,
-                      lora=lora_config(cfg), lora_backward=cfg.lora_backward)
+                      lora=lora_config(cfg), lora_backward=cfg.lora_backward, sam=sam_config(cfg))
     start_epoch, step = 0, 0
     if cfg.mode == MODE_RESUME:
         trainer.load_state_dict(torch.load(os.path.join(cfg.ckpt_path, "trainer.pt"), map_location=model.device))
@@ -645,6 +672,8 @@ def apply_gpu_flag(args: argparse.Namespace, argv: Optional[List[str]]):
         return plan
     if getattr(args, "lora_r", None) is not None:                      # before the ranks start
         raise NotImplementedError("--lora_r on more than one GPU is not built")
+    if getattr(args, "sam_rho", None) is not None:
+        raise NotImplementedError("--sam_rho on more than one GPU is not built")
     import socket
     import subprocess
     with socket.socket() as sk:

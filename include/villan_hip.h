@@ -546,6 +546,41 @@ int vd_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, i
 /* a <-> b in place, n floats each, bit for bit (nothing is rounded; NaN payloads survive): 16-byte accesses where both pointers allow, 4-byte
  * otherwise.  The buffers must not overlap. */
 int vd_swap(float* a, float* b, int64_t n, void* stream);
+/* Sharpness-aware minimisation (trainer.py, Trainer(sam=...)): the perturbation w <- w + e between the two passes of a SAM step, with
+ * e_i = rho * T_i^2 g_i / ||T g||_2.  mode 0 (SAM): T_i = 1; mode 1 (ASAM): T_i = |w_i| + eta, in f32.  Plain C++ with vector loads and stores,
+ * no atomics, every operation rounded on its own (no FMA contraction), every sum in a fixed order: bit-reproducible.  The flat kernels walk
+ * the n floats in items of four from the buffer's start, item q in thread q % (grid * block) of the launch vd_sam_plan reports: one 16-byte
+ * access where every pointer is 16-byte aligned, four scalar ones otherwise (and for a last, partial item), with the same values and the
+ * same sums either way.  Pointers are 4-byte aligned.  VD_EINVAL before any launch: a mode outside {0, 1}, a negative or non-finite rho or
+ * eta, n < 0, a required pointer that is NULL, buffers that overlap.
+ *
+ * vd_sam_plan (host only): the launch shape of vd_sam_norm_sq's first stage and of vd_sam_perturb for n floats:
+ *   block = 256, floats_per_thread = 16, grid = clamp(ceil(n / (block * floats_per_thread)), 1, 1024); past the cap a thread strides on. */
+int vd_sam_plan(int64_t n, int* grid, int* block, int* floats_per_thread);
+/* *out_sq = sum_i u_i * u_i with u_i = T_i * g_i (mode 0: u_i = g_i; w may be NULL).  partial: >= 1024 floats of scratch.  Two stages:
+ *   1. a thread keeps one f32 partial per position k % 4 over its items in ascending order, adds them as (a0 + a1) + (a2 + a3); the 64 lanes
+ *      of a wave are added by a fixed xor tree, the four waves as (r0 + r1) + (r2 + r3); partial[workgroup] holds the result;
+ *   2. one workgroup: thread t adds partial[t], partial[t + 256], ... in that order, then the same tree.
+ * The longest chain of additions is ceil(ceil(n / 4) / (grid * block)) + ceil(grid / 256) + 18. */
+int vd_sam_norm_sq(const float* g, const float* w, int64_t n, int mode, float eta, float* partial, float* out_sq, void* stream);
+/* One pass: backup[i] = w[i] (bit for bit; backup may be NULL), then w[i] = w[i] + a * g[i] with c = rho / (sqrtf(*norm_sq) + 1e-12f) and a = c
+ * (mode 0) or a = (c * T_i) * T_i (mode 1, T_i from the w[i] just read).  *norm_sq is a device word.  If it is not finite or is 0, w is left
+ * as it is and backup is still written.  w, g and backup do not overlap.  A raw write of weights: the caller invalidates what it derived
+ * from them. */
+int vd_sam_perturb(float* w, const float* g, float* backup, int64_t n, int mode, float eta, float rho, const float* norm_sq, void* stream);
+/* The neuron-adaptive mode, over a NEURON TABLE (see vd_neuron_scale): T_j = sqrtf(wsq_j / len_j) + eta, the root mean square of weight row j
+ * plus eta, with wsq_j = sum_k w_jk^2 and gsq_j = sum_k g_jk^2 from vd_neuron_grad(w, w, ...) and vd_neuron_grad(g, g, ...).  wsq, gsq, coef:
+ * n_neurons floats.
+ *   *norm_sq = sum_j (T_j * T_j) * gsq_j;   coef[j] = ((rho / (sqrtf(*norm_sq) + 1e-12f)) * T_j) * T_j;   every coef[j] = 0 where *norm_sq
+ * is not finite or is 0.  One workgroup of 256 threads: thread t walks the jobs in table order and in each job the rows t, t + 256, ... in that
+ * order, all in ONE f32 chain; the 256 chains are added by the xor tree of a wave and the four waves as (r0 + r1) + (r2 + r3).  The longest
+ * chain of additions is sum over the jobs of ceil(rows / 256), plus 8. */
+int vd_sam_neuron_coef(const float* wsq, const float* gsq, const int64_t* table, int n_jobs, int64_t n_neurons, float rho, float eta, float* coef,
+                       float* norm_sq, void* stream);
+/* w[row j][k] = w[row j][k] + coef[j] * g[row j][k] for every weight row of the table, in vd_neuron_scale's layout (one wave per row, four rows
+ * per workgroup; an aligned row moves as f32x4, any other as scalars, with the same values).  Biases and every float outside the table's rows
+ * are not written.  w != g. */
+int vd_neuron_axpy(float* w, const float* g, const int64_t* table, int n_jobs, int64_t total_blocks, const float* coef, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10 -- sampler steps (diffusers *Scheduler.step, via pipeline(...) VillanDiffusion.py:579).

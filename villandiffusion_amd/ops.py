@@ -1317,6 +1317,65 @@ def swap(a, b):
         _lib().vd_swap(_p(a), _p(b), a.numel(), _s()), "vd_swap"))
 
 
+SAM_MODES = {"sam": 0, "asam": 1}
+
+
+def sam_plan(n: int):
+    """(grid, block, floats per thread) of vd_sam_norm_sq's first stage and of vd_sam_perturb for n floats: asked of the library on the host."""
+    g, b, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    L.check(L.load().vd_sam_plan(int(n), C.byref(g), C.byref(b), C.byref(f)), "vd_sam_plan")
+    return g.value, b.value, f.value
+
+
+def _sam_flat(*ts):
+    n = ts[0].numel()
+    for t in ts:
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n and t.device == ts[0].device), "flat f32 buffers"
+    return n
+
+
+def sam_norm_sq(g, w, partial, out_sq, mode="asam", eta=0.01):
+    """out_sq = sum (T g)^2 with T = 1 ("sam"; w may be None) or |w| + eta ("asam") (vd_sam_norm_sq: two stages in a fixed order)."""
+    n = _sam_flat(g, w)
+    assert partial.numel() >= 1024 and partial.dtype == torch.float32
+    m = SAM_MODES[mode]
+    _timed("sam_norm_sq (sam_norm_kernel)", 4.0 * n * (1 + m), "hbm", lambda: L.check(                   # g read, and w in "asam"
+        _lib().vd_sam_norm_sq(_p(g), _p(w), n, m, float(eta), _p(partial), _p(out_sq), _s()), "vd_sam_norm_sq"))
+    return out_sq
+
+
+def sam_perturb(w, g, backup, norm_sq, rho, mode="sam", eta=0.01):
+    """backup = w (bit for bit; None: no copy), then w += a g with c = rho / (sqrt(norm_sq) + 1e-12) and a = c ("sam") or (c T) T with
+    T = |w| + eta ("asam") (vd_sam_perturb: one pass; a norm that is 0 or not finite leaves w alone).  A raw-pointer write: whoever perturbs
+    network weights bumps WEIGHTS_EPOCH and calls the network's weights_changed() afterwards (as with `swap`)."""
+    n = _sam_flat(w, g, backup)
+    _timed("sam_perturb (sam_perturb_kernel)", 4.0 * n * (3 + (backup is not None)), "hbm", lambda: L.check(    # w, g read; w, backup written
+        _lib().vd_sam_perturb(_p(w), _p(g), _p(backup), n, SAM_MODES[mode], float(eta), float(rho), _p(norm_sq), _s()), "vd_sam_perturb"))
+    return w
+
+
+def sam_neuron_coef(wsq, gsq, tab, coef, norm_sq, rho, eta=0.01):
+    """norm_sq = sum_j T_j^2 gsq_j and coef[j] = rho / (sqrt(norm_sq) + 1e-12) * T_j * T_j with T_j = sqrt(wsq_j / len_j) + eta, one value per
+    neuron of `tab` (vd_sam_neuron_coef: one workgroup, fixed order; a norm that is 0 or not finite gives coef = 0)."""
+    for v in (wsq, gsq, coef):
+        assert v.is_contiguous() and v.dtype == torch.float32 and v.numel() == tab.n_neurons and v.device == wsq.device, "one f32 per neuron"
+    table = tab.device_table(wsq.device)
+    _timed("sam_neuron_coef (sam_neuron_coef_kernel)", 20.0 * tab.n_neurons, "hbm", lambda: L.check(     # wsq, gsq read twice; coef written
+        _lib().vd_sam_neuron_coef(_p(wsq), _p(gsq), _p(table), tab.n_jobs, tab.n_neurons, float(rho), float(eta), _p(coef), _p(norm_sq), _s()),
+        "vd_sam_neuron_coef"))
+    return coef
+
+
+def neuron_axpy(w, g, tab, coef):
+    """w[row j] += coef[j] * g[row j] for every weight row of `tab`; biases and every float outside the table keep their bits (vd_neuron_axpy: one
+    launch, vd_neuron_scale's layout).  A raw-pointer write: the caller bumps WEIGHTS_EPOCH and calls weights_changed() (as with `swap`)."""
+    table = _neuron_args(tab, w, coef)
+    assert g.is_contiguous() and g.dtype == torch.float32 and g.numel() >= tab.extent and g.data_ptr() != w.data_ptr()
+    _timed("neuron_axpy (neuron_axpy_kernel)", 12.0 * tab.weight_floats + 4.0 * tab.n_neurons, "hbm", lambda: L.check(   # w, g read; w written
+        _lib().vd_neuron_axpy(_p(w), _p(g), _p(table), tab.n_jobs, tab.total_blocks, _p(coef), _s()), "vd_neuron_axpy"))
+    return w
+
+
 # --------------------------------------------------------------------------------------------- samplers / data
 def sched_step(x, eps, out, *, c_eps, c_div, clip, c_x0, c_x, c_e, c_z, z=None, x0_out=None, seed=0, offset=0):
     assert x.is_contiguous() and eps.is_contiguous() and out.is_contiguous()

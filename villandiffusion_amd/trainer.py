@@ -51,6 +51,52 @@ def ema_one_minus_decay(k: int, cfg: EMAConfig) -> float:
     return ctypes.c_float(1.0 - ema_decay_at(k, cfg)).value
 
 
+SAM_MODES = ("sam", "asam", "neuron")
+
+
+@dataclass
+class SAMConfig:
+    """Sharpness-aware minimisation: every optimiser step takes its gradient at w + e, e = rho * T^2 g / ||T g|| with g the gradient at w.
+    mode "sam" (Foret et al. 2021): T = 1; "asam" (Kwon et al. 2021): T_i = |w_i| + eta; "neuron": one T per neuron of
+    ``anp.neuron_table(model, layers)``, the root mean square of its weight row plus eta -- neurons with large weights are perturbed more, in the
+    spirit of FT-SAM (Zhu et al. 2023), and only those weight rows are perturbed.  ``layers`` is read by "neuron" alone."""
+    rho: float
+    mode: str = "sam"
+    eta: float = 0.01
+    layers: str = "conv"
+
+    def __post_init__(self):
+        from .anp import LAYERS
+        if isinstance(self.rho, bool) or not isinstance(self.rho, (int, float)) or not math.isfinite(self.rho) or self.rho <= 0:
+            raise ValueError(f"SAMConfig: rho must be a positive finite number, got {self.rho!r}")
+        if isinstance(self.eta, bool) or not isinstance(self.eta, (int, float)) or not math.isfinite(self.eta) or self.eta < 0:
+            raise ValueError(f"SAMConfig: eta must be a finite number >= 0, got {self.eta!r}")
+        if self.mode not in SAM_MODES:
+            raise ValueError(f"SAMConfig: mode must be one of {SAM_MODES}, got {self.mode!r}")
+        if self.layers not in LAYERS:
+            raise ValueError(f"SAMConfig: layers must be one of {LAYERS}, got {self.layers!r}")
+
+
+def check_sam(sam, grad_accum: int = 1, lora=None, graph_micro_step: Optional[bool] = None, world: int = 1, conv_math: Optional[str] = None):
+    """What a SAM trainer is not built for, each refusal saying which; pure host code, shared by Trainer and the drivers' setup()."""
+    if sam is None:
+        return
+    if not isinstance(sam, SAMConfig):
+        raise TypeError(f"Trainer: sam must be a SAMConfig, got {type(sam).__name__}")
+    if max(1, int(grad_accum)) > 1:
+        raise ValueError(f"Trainer: sam with grad_accum={grad_accum} is not built (the second pass would have to replay the whole accumulation "
+                         f"window at the perturbed weights); use grad_accum=1")
+    if lora is not None:
+        raise ValueError("Trainer: sam together with lora is not built (the perturbation belongs to the adapter, which SAM does not see)")
+    if graph_micro_step:
+        raise ValueError("Trainer: sam with graph_micro_step=True is not built (a SAM step runs its two passes eagerly)")
+    if world > 1:
+        raise NotImplementedError("Trainer: sam in a process group of more than one rank is not built (the first pass's gradient would need an "
+                                  "all-reduce of its own)")
+    if conv_math == "f16":
+        raise NotImplementedError("Trainer: sam with conv_math='f16' is not built (an overflow in the first pass has no skip path)")
+
+
 class FusedAdam:
     """torch.optim.Adam(betas=(0.9, 0.999), eps=1e-8, weight_decay=0) on one flat buffer, with the global-norm clip
     fused in.  ``state_dict`` is flat too (exp_avg / exp_avg_sq / step).  With an ``EMAConfig`` the same launch keeps ``self.ema``, the
@@ -253,12 +299,17 @@ class GraphedMicroStep:
 class Trainer:
     def __init__(self, model, loss_fn, lr: float, total_steps: int, warmup_steps: int = 500, grad_accum: int = 1,
                  max_grad_norm: Optional[float] = 1.0, n_allreduce_buckets: int = 4, graph_micro_step: Optional[bool] = None,
-                 force_ddp_path: bool = False, ema: Optional[EMAConfig] = None, lora=None, lora_backward: Optional[str] = None):
-        """lora_backward (with lora only; None means "full"): "full" -- the backward forms every weight gradient; "adapted" -- only what the
+                 force_ddp_path: bool = False, ema: Optional[EMAConfig] = None, lora=None, lora_backward: Optional[str] = None,
+                 sam: Optional[SAMConfig] = None):
+        """sam: a SAMConfig makes every optimiser step a sharpness-aware one (`_sam_micro_step`); None changes nothing.
+        lora_backward (with lora only; None means "full"): "full" -- the backward forms every weight gradient; "adapted" -- only what the
         adapter needs (lora.BackwardRoute; UNet2DModel).  The mode belongs to the run: no state records it, a state of either loads in both."""
         self.model, self.loss_fn = model, loss_fn
         self.base_lr = lr
         self.adapter = None
+        check_sam(sam, grad_accum, lora, graph_micro_step, dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1,
+                  getattr(model, "conv_math", None))              # every SAM refusal comes before the first launch
+        self.sam = sam
         if lora is None and lora_backward is not None:
             raise ValueError(f"Trainer: lora_backward={lora_backward!r} needs lora=LoRAConfig(...)")
         if lora is not None:
@@ -299,6 +350,9 @@ class Trainer:
         # HIP-graph replay of the micro-step: on by default where a step is launch-bound (gradient accumulation = small micro-batches), single process
         self.graph_micro_step = (self.grad_accum > 1) if graph_micro_step is None else bool(graph_micro_step)
         self._graphs: Dict = {}
+        self.sam_loss_perturbed: Optional[torch.Tensor] = None      # the loss of a SAM step's second pass (device, no sync)
+        if sam is not None:
+            self._sam_init()
         # force_ddp_path: the schedule of a multi-rank step (bucket hooks fired from the explicit backward, eager micro-step, one all-reduce per
         # bucket) on a process group of ANY size, including 1 -- what rank 0 of an 8-GPU run executes minus the wire time (bench.py --ddp-path)
         self.ddp_path = (self.world > 1 or (force_ddp_path and dist.is_available() and dist.is_initialized())) and hasattr(model, "grad_buckets")
@@ -395,6 +449,79 @@ class Trainer:
         ops.WEIGHTS_EPOCH += 1                           # caches keyed on (flat_param._version, WEIGHTS_EPOCH): transposed weights, packed operands
         self.model.weights_changed()
 
+    # ---- sharpness-aware minimisation ------------------------------------------------------------------------------------------------------
+    def _sam_init(self):
+        """The buffers of a SAM step, allocated once: the backup of the weights, the norm word and, in "neuron" mode, the table and three floats
+        per neuron."""
+        cfg, fp = self.sam, self.model.flat_param
+        self._sam_rho = float(cfg.rho)                     # (what the launches read)
+        self._sam_backup = torch.empty_like(fp)
+        self._sam_norm_sq = torch.zeros(1, device=fp.device, dtype=torch.float32)
+        self._sam_partial = torch.empty(1024, device=fp.device, dtype=torch.float32)
+        self._sam_tab = None
+        if cfg.mode == "neuron":
+            from .anp import neuron_table
+            self._sam_tab = neuron_table(self.model, cfg.layers)
+            self._sam_wsq, self._sam_gsq, self._sam_coef = (torch.zeros(self._sam_tab.n_neurons, device=fp.device, dtype=torch.float32)
+                                                            for _ in range(3))
+
+    def _sam_perturb(self):
+        """flat_param <- w + e(g), g = flat_grad, and the backup <- w: the norm and the perturbation as single launches over the flat buffers,
+        nothing read back.  A raw-pointer write, so the operands derived from the weights are dropped (as in `_swap_ema`)."""
+        cfg, m = self.sam, self.model
+        w, g, nsq = m.flat_param, m.flat_grad, self._sam_norm_sq
+        if cfg.mode == "neuron":
+            tab = self._sam_tab
+            ops.neuron_grad(w, w, tab, self._sam_wsq)
+            ops.neuron_grad(g, g, tab, self._sam_gsq)
+            ops.sam_neuron_coef(self._sam_wsq, self._sam_gsq, tab, self._sam_coef, nsq, self._sam_rho, cfg.eta)
+            with torch.no_grad():
+                self._sam_backup.copy_(w)
+            ops.neuron_axpy(w, g, tab, self._sam_coef)
+        else:
+            if cfg.mode == "sam":
+                ops.l2norm_sq(g, self._sam_partial, nsq)
+            else:
+                ops.sam_norm_sq(g, w, self._sam_partial, nsq, "asam", cfg.eta)
+            ops.sam_perturb(w, g, self._sam_backup, nsq, self._sam_rho, cfg.mode, cfg.eta)
+        ops.WEIGHTS_EPOCH += 1
+        m.weights_changed()
+
+    def _sam_restore(self):
+        with torch.no_grad():
+            self.model.flat_param.copy_(self._sam_backup)
+        ops.WEIGHTS_EPOCH += 1
+        self.model.weights_changed()
+
+    def _sam_micro_step(self, batch, timesteps, noise, target_key, poison_key):
+        """Both passes of a SAM step on one batch, timesteps, noise and poison flags; leaves the gradient at w + e in flat_grad and the network
+        at w (also after an exception in the second pass), and returns the loss at w."""
+        m, lf = self.model, self.loss_fn
+        if getattr(m, "conv_math", None) == "f16":
+            raise NotImplementedError("Trainer: sam with conv_math='f16' is not built (an overflow in the first pass has no skip path)")
+        if noise is None:                                  # drawn once, as LossFn.p_loss would: a SAM step consumes the stream like a plain one
+            noise = lf._noise(batch[target_key].to(m.device).float())
+
+        def one_pass():
+            loss = lf.p_loss_by_keys(batch, m, target_latent_key=target_key, poison_latent_key=poison_key, timesteps=timesteps, noise=noise)
+            loss.backward()
+            return loss
+
+        sync_now, self._sync_now = self._sync_now, False   # (the bucket hooks of the multi-rank schedule belong to the second pass)
+        loss = one_pass()
+        kept = (lf.last_sample_loss, lf.last_split)        # a shaped loss's readouts of pass 1: a few floats, cloned before pass 2 refills them
+        if getattr(lf, "shaped", False):
+            kept = tuple(None if v is None else v.clone() for v in kept)
+        self._sam_perturb()
+        try:
+            m.zero_grad()
+            self._sync_now = sync_now
+            self.sam_loss_perturbed = one_pass().detach()
+        finally:
+            self._sam_restore()
+        lf.last_sample_loss, lf.last_split = kept
+        return loss
+
     def train_step(self, batch, timesteps: torch.Tensor, noise: Optional[torch.Tensor] = None, last_batch: bool = False,
                    target_key: str = "target", poison_key: str = "pixel_values"):
         """One micro-step; returns the (un-divided) loss tensor of this micro-batch."""
@@ -405,7 +532,10 @@ class Trainer:
         if self.micro % self.grad_accum == 0:                          # first micro-step of an accumulation window (the scale never changes inside one)
             self._step_scale = self._scale()
         self.loss_fn.grad_scale = self._step_scale / self.grad_accum
-        loss = self._graphed(batch, timesteps, noise, target_key, poison_key)
+        if self.sam is not None and len(batch[target_key]) > 0:
+            loss = self._sam_micro_step(batch, timesteps, noise, target_key, poison_key)
+        else:
+            loss = self._graphed(batch, timesteps, noise, target_key, poison_key)
         if loss is None:
             loss = self.loss_fn.p_loss_by_keys(batch, self.model, target_latent_key=target_key, poison_latent_key=poison_key,
                                                timesteps=timesteps, noise=noise)
@@ -459,6 +589,8 @@ class Trainer:
               "loss_scale": self.loss_scale, "since_growth": self._since_growth, "overflow_steps_seen": self.overflow_steps_seen}
         if self.adapter is not None:
             sd["lora"] = self.adapter.train_state()
+        if self.sam is not None:
+            sd["sam"] = asdict(self.sam)                 # for information only: SAM keeps no state between steps, load_state_dict ignores it
         return sd
 
     def load_state_dict(self, sd: Dict):
