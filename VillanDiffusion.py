@@ -44,12 +44,13 @@ IGNORE_ARGS = {"overwrite", "is_save_all_model_epochs", "R_trigger_only"}
 # --lora_r / --lora_alpha / --lora_target / --lora_backward (train modes: a LoRA fine-tune, villandiffusion_amd.lora; resume takes them from
 # args.json), --snr_gamma / --poison_loss_weight / --log_loss_split (train modes: the shaped loss, villandiffusion_amd.loss.LossFn snr_gamma /
 # poison_weight / track_split; resume takes them from args.json), --sam_rho / --sam_mode / --sam_eta / --sam_layers (train modes: sharpness-aware
-# steps, villandiffusion_amd.trainer.SAMConfig; resume takes them from args.json).
+# steps, villandiffusion_amd.trainer.SAMConfig; resume takes them from args.json), --keep_pruned (train modes: a prune_mask.pt of
+# tools/fine_prune.py whose rows the fine-tune holds at zero, Trainer(keep_pruned=...); resume takes it from args.json).
 # At their defaults they are left out of the JSON side files, which then read as they did before the options existed.
 EXTRA_MODE_OPTS = {MODE_SAMPLING: {"use_ema"}, MODE_MEASURE: {"use_ema"}}
 EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False, "lora_r": None, "lora_alpha": None, "lora_target": "attn", "lora_backward": None,
                   "snr_gamma": None, "poison_loss_weight": 1.0, "log_loss_split": False,
-                  "sam_rho": None, "sam_mode": None, "sam_eta": None, "sam_layers": None}
+                  "sam_rho": None, "sam_mode": None, "sam_eta": None, "sam_layers": None, "keep_pruned": None}
 
 
 def _side_file(d: dict) -> dict:
@@ -94,6 +95,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     # not in the reference: sharpness-aware steps (SAM / ASAM / neuron-adaptive): the gradient of every optimiser step is taken at perturbed weights
     a("--sam_rho", type=float); a("--sam_mode", type=str, choices=["sam", "asam", "neuron"]); a("--sam_eta", type=float)
     a("--sam_layers", type=str, choices=["conv", "all"])
+    # not in the reference: hold the rows a prune mask names (tools/fine_prune.py writes prune_mask.pt) at zero through the fine-tune
+    a("--keep_pruned", type=str)
     return p.parse_args(argv)
 
 
@@ -118,6 +121,7 @@ class TrainingConfig:
     lora_r: Optional[int] = None; lora_alpha: Optional[float] = None; lora_target: str = "attn"; lora_backward: Optional[str] = None
     snr_gamma: Optional[float] = None; poison_loss_weight: float = 1.0; log_loss_split: bool = False
     sam_rho: Optional[float] = None; sam_mode: Optional[str] = None; sam_eta: Optional[float] = None; sam_layers: Optional[str] = None
+    keep_pruned: Optional[str] = None
     extra: dict = field(default_factory=dict)
 
 
@@ -183,6 +187,7 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
         raise ValueError(f"batch size {cfg.batch} should be smaller or equal to {bs} for dataset {cfg.dataset}")
     cfg.gradient_accumulation_steps = int(bs // cfg.batch)
     sam_config(cfg)                                                    # ValueError / NotImplementedError before anything is created
+    keep_pruned_mask(cfg)
     # One process per GPU (torchrun): every rank computes the same config, but the existing-directory check, the directory
     # creation and the JSON side files belong to rank 0 alone -- main() puts a barrier behind it.  (The reference is a single
     # process driving nn.DataParallel, :440, so it has no such distinction.)
@@ -248,6 +253,19 @@ def sam_config(cfg: TrainingConfig):
         check_sam(sc, cfg.gradient_accumulation_steps, lora=cfg.lora_r, world=world,
                   conv_math="f16" if getattr(cfg, "mixed_precision", "no") == "fp16" else None)
     return sc
+
+
+def keep_pruned_mask(cfg: TrainingConfig):
+    """The PruneMask --keep_pruned names (a prune_mask.pt, or a directory that holds one), or None.  In the train modes it raises what Trainer
+    would for the combinations a masked fine-tune is not built with (LoRA, SAM, more than one GPU), before a device is touched."""
+    if cfg.keep_pruned is None or cfg.mode not in (MODE_TRAIN, MODE_RESUME, MODE_TRAIN_MEASURE):      # (sampling reads no mask)
+        return None
+    from villandiffusion_amd.actprune import PruneMask
+    from villandiffusion_amd.trainer import check_keep_pruned
+    mask = PruneMask.load(cfg.keep_pruned)                             # FileNotFoundError / ValueError for what is no mask
+    world = max(len(str(cfg.gpu).split(",")), int(os.environ.get("WORLD_SIZE", "1")))
+    check_keep_pruned(mask, lora=cfg.lora_r, sam=cfg.sam_rho, world=world)
+    return mask
 
 
 def loss_shaping(cfg: TrainingConfig) -> dict:
@@ -558,7 +576,8 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
     n_batch = (len(dsl) + cfg.batch * world - 1) // (cfg.batch * world)
     trainer = Trainer(model, loss_fn, lr=cfg.learning_rate, total_steps=n_batch * cfg.epoch, warmup_steps=cfg.lr_warmup_steps,
                       grad_accum=cfg.gradient_accumulation_steps, ema=EMAConfig(decay=cfg.ema_decay) if cfg.ema_decay is not None else None,
-                      lora=lora_config(cfg), lora_backward=cfg.lora_backward, sam=sam_config(cfg))
+                      lora=lora_config(cfg), lora_backward=cfg.lora_backward, sam=sam_config(cfg),
+                      keep_pruned=keep_pruned_mask(cfg))
     start_epoch, step = 0, 0
     if cfg.mode == MODE_RESUME:
         trainer.load_state_dict(torch.load(os.path.join(cfg.ckpt_path, "trainer.pt"), map_location=model.device))
@@ -674,6 +693,8 @@ def apply_gpu_flag(args: argparse.Namespace, argv: Optional[List[str]]):
         raise NotImplementedError("--lora_r on more than one GPU is not built")
     if getattr(args, "sam_rho", None) is not None:
         raise NotImplementedError("--sam_rho on more than one GPU is not built")
+    if getattr(args, "keep_pruned", None) is not None:
+        raise NotImplementedError("--keep_pruned on more than one GPU is not built")
     import socket
     import subprocess
     with socket.socket() as sk:

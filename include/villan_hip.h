@@ -581,6 +581,39 @@ int vd_sam_neuron_coef(const float* wsq, const float* gsq, const int64_t* table,
  * per workgroup; an aligned row moves as f32x4, any other as scalars, with the same values).  Biases and every float outside the table's rows
  * are not written.  w != g. */
 int vd_neuron_axpy(float* w, const float* g, const int64_t* table, int n_jobs, int64_t total_blocks, const float* coef, void* stream);
+/* Activation-based channel pruning (actprune.py) -- csrc/vd_actstat.hip.
+ *
+ * vd_channel_stats: per-channel sums of a hidden activation for a whole network.  A JOB TABLE of n_jobs x 11 int64, one job per tapped tensor,
+ * is given twice: `host_table` in host memory (every job is checked there before any launch) and `table`, the same bytes in device memory.  A
+ * job is
+ *   {address of x, address of mean, address of rstd, address of gamma, address of beta, B, C, HW, G, first channel, first workgroup}
+ * with x f32 [B, C, HW] contiguous, mean and rstd [B, G], gamma and beta [C].  First channels ascend and the channel ranges do not overlap;
+ * a job owns the workgroups vd_channel_stats_plan reports, first workgroups ascend from 0 by that count (the neuron-table convention).
+ *   act = 0:  a = x; the four statistics addresses are not read and may be 0.
+ *   act = 1:  a = z * sigmoid(z), z = fma((x - mean[b][g]) * rstd[b][g], gamma[c], beta[c]), g = c / (C / G), every other operation rounded
+ *             on its own: the order of vd_groupnorm_fwd's element path and its sigmoid (1 ulp hardware reciprocal of 1 + exp(-z)) with SiLU
+ *             on.  (Its register, wave and chunk kernels fold the same map into fma(x, gamma * rstd, beta - mean * gamma * rstd).)
+ *   out[2 * (first channel + c) + {0, 1}] = {sum of a, sum of a * a} over b and p, f32, WRITTEN (never accumulated); out holds out_channels
+ *   pairs.
+ * No atomics; every sum in a fixed order: bit-reproducible.  The channel is walked in items of four consecutive floats of one image's run
+ * (I = ceil(HW / 4) items per run, B * I per channel, item q = b * I + i) and cut into S segments of L = ceil(B * I / S) items, S =
+ * clamp(ceil(B * I / 1024), 1, 256).  One 64-lane wave sums one (channel, segment): lane l takes the items lo + l, lo + l + 64, ... in that
+ * order, one f32 partial per position of an item, added as (a0 + a1) + (a2 + a3), the lanes by a fixed xor tree.  With S > 1 the pairs are
+ * parked in `ws` and a second launch adds a channel's S pairs in index order.  The longest chain of additions is
+ *   ceil(L / 64) + 8 + (S - 1).
+ * An item is one 16-byte load where x is 16-byte aligned and HW % 4 == 0, four scalar loads otherwise, with the same values and sums either
+ * way.  x is read once; nothing but out and ws is written.  ws: >= vd_channel_stats_ws_floats floats (0: may be NULL).
+ * VD_EINVAL before any launch: n_jobs < 1, act outside {0, 1}, C % G != 0, a null x, a null statistics address with act = 1, first
+ * channels or workgroups that break the rules above, an out or ws that is too small.
+ * vd_channel_stats_plan (host only): workgroups of a job, segments S per channel, and the chain length above. */
+int vd_channel_stats_plan(int B, int C, int64_t HW, int* workgroups, int* segments, int64_t* chain);
+int64_t vd_channel_stats_ws_floats(const int64_t* host_table, int n_jobs);      /* -1: an invalid table */
+int vd_channel_stats(const int64_t* host_table, const int64_t* table, int n_jobs, int act, float* out, int64_t out_channels, float* ws,
+                     int64_t ws_floats, void* stream);
+/* buf[row j][k] = +0.0f for every weight row j of a NEURON TABLE (see vd_neuron_scale) with keep[first neuron + j] == 0.0f, in place, in
+ * vd_neuron_scale's layout (one wave per row; an aligned row moves as f32x4, any other as scalars).  Every other float of buf -- kept rows,
+ * biases, floats outside the table -- is neither read nor written.  One launch for the network. */
+int vd_neuron_keep_rows(float* buf, const int64_t* table, int n_jobs, int64_t total_blocks, const float* keep, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10 -- sampler steps (diffusers *Scheduler.step, via pipeline(...) VillanDiffusion.py:579).

@@ -1376,6 +1376,70 @@ def neuron_axpy(w, g, tab, coef):
     return w
 
 
+CHANNEL_ACTS = {"raw": 0, "silu_gn": 1}
+CHANNEL_JOB_INTS = 11     # x, mean, rstd, gamma, beta, B, C, HW, G, first channel, first workgroup
+
+
+def channel_stats_plan(Bn: int, Cc: int, HW: int):
+    """(workgroups of a [B, C, HW] job, segments a channel is cut into, longest chain of additions of a sum) of vd_channel_stats: asked of the
+    library on the host."""
+    wg, seg, chain = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    L.check(L.load().vd_channel_stats_plan(int(Bn), int(Cc), int(HW), C.byref(wg), C.byref(seg), C.byref(chain)), "vd_channel_stats_plan")
+    return wg.value, seg.value, chain.value
+
+
+def channel_stats_table(taps):
+    """The host job table of vd_channel_stats ([n_jobs, 11] int64) for taps = [(x [B, C, ...] contiguous f32, mean, rstd, gamma, beta, G,
+    first channel)] (the four statistics tensors None: address 0, for act "raw").  -> (table, n_channels written up to)."""
+    rows, block, top = [], 0, 0
+    for x, mean, rstd, gamma, beta, G, c0 in taps:
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.dim() >= 2, "a tapped tensor is contiguous f32 [B, C, ...]"
+        Bn, Cc = int(x.shape[0]), int(x.shape[1])
+        HW = x.numel() // (Bn * Cc)
+        for v, n in ((mean, Bn * G), (rstd, Bn * G), (gamma, Cc), (beta, Cc)):
+            assert v is None or (v.is_contiguous() and v.dtype == torch.float32 and v.numel() == n and v.device == x.device), "statistics shape"
+        ad = lambda v: 0 if v is None else v.data_ptr()
+        rows.append((x.data_ptr(), ad(mean), ad(rstd), ad(gamma), ad(beta), Bn, Cc, HW, int(G), int(c0), block))
+        block += channel_stats_plan(Bn, Cc, HW)[0]
+        top = max(top, int(c0) + Cc)
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, CHANNEL_JOB_INTS), top
+
+
+def channel_stats(taps, out, act="silu_gn", keep=None):
+    """out[first channel + c] = (sum a, sum a^2) over the batch and the pixels of channel c of every tap, a = x ("raw") or silu(groupnorm(x))
+    from the given mean / rstd / gamma / beta ("silu_gn") (vd_channel_stats: one launch for the table, a second one where a channel is long
+    enough to be cut; fixed order, bit-reproducible).  out: [n_channels, 2] f32, written where the taps point.  The tapped tensors must stay
+    alive until the launch has run; `keep` (a list) receives the table and the workspace, which must live as long."""
+    dev = out.device
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2 and out.shape[1] == 2
+    host, top = channel_stats_table(taps)
+    assert top <= out.shape[0], (top, tuple(out.shape))
+    n_jobs = host.shape[0]
+    ws_n = int(L.load().vd_channel_stats_ws_floats(host.data_ptr(), n_jobs))
+    if ws_n < 0:
+        raise L.VillanHipError(f"vd_channel_stats: {L.last_error()}")
+    ws = torch.empty(ws_n, device=dev, dtype=torch.float32) if ws_n else None
+    table = upload_table(host, dev)
+    if keep is not None:
+        keep += [table, ws]
+    nbytes = 4.0 * sum(t[0].numel() for t in taps) + 8.0 * top
+    _timed("channel_stats (channel_stats_kernel)", nbytes, "hbm", lambda: L.check(          # every x read once; one pair per channel written
+        _lib().vd_channel_stats(host.data_ptr(), _p(table), n_jobs, CHANNEL_ACTS[act], _p(out), int(out.shape[0]), _p(ws), ws_n, _s()),
+        "vd_channel_stats"))
+    return out
+
+
+def neuron_keep_rows(buf, tab, keep):
+    """buf[row j] = +0.0 for every weight row of `tab` with keep[j] == 0, in place; kept rows, biases and every float outside the table keep
+    their bits (vd_neuron_keep_rows: one launch, vd_neuron_scale's layout).  On network weights a raw-pointer write: the caller bumps
+    WEIGHTS_EPOCH and calls weights_changed() (as with `swap`)."""
+    table = _neuron_args(tab, buf, keep)
+    assert keep.device == buf.device
+    _timed("neuron_keep_rows (neuron_keep_rows_kernel)", 4.0 * tab.n_neurons, "hbm", lambda: L.check(    # the mask read; only dropped rows written
+        _lib().vd_neuron_keep_rows(_p(buf), _p(table), tab.n_jobs, tab.total_blocks, _p(keep), _s()), "vd_neuron_keep_rows"))
+    return buf
+
+
 # --------------------------------------------------------------------------------------------- samplers / data
 def sched_step(x, eps, out, *, c_eps, c_div, clip, c_x0, c_x, c_e, c_z, z=None, x0_out=None, seed=0, offset=0):
     assert x.is_contiguous() and eps.is_contiguous() and out.is_contiguous()

@@ -97,6 +97,24 @@ def check_sam(sam, grad_accum: int = 1, lora=None, graph_micro_step: Optional[bo
         raise NotImplementedError("Trainer: sam with conv_math='f16' is not built (an overflow in the first pass has no skip path)")
 
 
+def check_keep_pruned(keep_pruned, lora=None, sam=None, world: int = 1):
+    """What a masked fine-tune is not built with, each refusal saying which; pure host code, shared by Trainer and the drivers' setup()."""
+    if keep_pruned is None:
+        return
+    from .actprune import PruneMask
+    if not isinstance(keep_pruned, PruneMask):
+        raise TypeError(f"Trainer: keep_pruned must be an actprune.PruneMask, got {type(keep_pruned).__name__}")
+    if lora is not None:
+        raise ValueError("Trainer: keep_pruned together with lora is not built (the merge W0 + s B A writes every row; the adapter would need "
+                         "the mask on B)")
+    if sam is not None:
+        raise ValueError("Trainer: keep_pruned together with sam is not built (the first pass's gradient would perturb the pruned rows away "
+                         "from zero for the second pass; it needs a mask launch between the passes)")
+    if world > 1:
+        raise NotImplementedError("Trainer: keep_pruned in a process group of more than one rank is not built (the mask launch would have to "
+                                  "follow the bucketed all-reduce)")
+
+
 class FusedAdam:
     """torch.optim.Adam(betas=(0.9, 0.999), eps=1e-8, weight_decay=0) on one flat buffer, with the global-norm clip
     fused in.  ``state_dict`` is flat too (exp_avg / exp_avg_sq / step).  With an ``EMAConfig`` the same launch keeps ``self.ema``, the
@@ -253,7 +271,8 @@ class GraphedMicroStep:
         n = self.net
         route = getattr(n, "lora_route", None)
         return (n.conv_math, n.wgrad_stream, n.group_wgrad, n.flat_param.data_ptr(), n.flat_grad.data_ptr(), self.trainer.loss_fn.grad_scale,
-                None if route is None else (id(route), route.gab.data_ptr()), getattr(self.trainer.loss_fn, "shaping", None))
+                None if route is None else (id(route), route.gab.data_ptr()), None if self.trainer._keep is None else self.trainer._keep.data_ptr(),      # the mask launch's operand
+                getattr(self.trainer.loss_fn, "shaping", None))
 
     def valid(self) -> bool:
         dev = self.net.device
@@ -272,6 +291,8 @@ class GraphedMicroStep:
         else:
             ops.mse_fwd_bwd(pred, y, dpred, self.loss, lf._partial, pscale=None, gscale=lf.grad_scale, kind=lf._loss_type)
         net._run_backward(st, dpred)
+        if self.trainer._keep is not None:                # masking is idempotent: every replay leaves the accumulated gradient masked
+            self.trainer._keep_grad()
 
     def __call__(self, x0, R, noise, t, flags=None):
         net = self.net
@@ -300,8 +321,9 @@ class Trainer:
     def __init__(self, model, loss_fn, lr: float, total_steps: int, warmup_steps: int = 500, grad_accum: int = 1,
                  max_grad_norm: Optional[float] = 1.0, n_allreduce_buckets: int = 4, graph_micro_step: Optional[bool] = None,
                  force_ddp_path: bool = False, ema: Optional[EMAConfig] = None, lora=None, lora_backward: Optional[str] = None,
-                 sam: Optional[SAMConfig] = None):
-        """sam: a SAMConfig makes every optimiser step a sharpness-aware one (`_sam_micro_step`); None changes nothing.
+                 sam: Optional[SAMConfig] = None, keep_pruned=None):
+        """keep_pruned: an actprune.PruneMask holds the pruned weight rows at +0.0 through the fine-tune (`_keep_init`); None changes nothing.
+        sam: a SAMConfig makes every optimiser step a sharpness-aware one (`_sam_micro_step`); None changes nothing.
         lora_backward (with lora only; None means "full"): "full" -- the backward forms every weight gradient; "adapted" -- only what the
         adapter needs (lora.BackwardRoute; UNet2DModel).  The mode belongs to the run: no state records it, a state of either loads in both."""
         self.model, self.loss_fn = model, loss_fn
@@ -310,6 +332,7 @@ class Trainer:
         check_sam(sam, grad_accum, lora, graph_micro_step, dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1,
                   getattr(model, "conv_math", None))              # every SAM refusal comes before the first launch
         self.sam = sam
+        check_keep_pruned(keep_pruned, lora, sam, dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1)
         if lora is None and lora_backward is not None:
             raise ValueError(f"Trainer: lora_backward={lora_backward!r} needs lora=LoRAConfig(...)")
         if lora is not None:
@@ -353,6 +376,9 @@ class Trainer:
         self.sam_loss_perturbed: Optional[torch.Tensor] = None      # the loss of a SAM step's second pass (device, no sync)
         if sam is not None:
             self._sam_init()
+        self.keep_pruned, self._keep, self._keep_tab = keep_pruned, None, None
+        if keep_pruned is not None:
+            self._keep_init()
         # force_ddp_path: the schedule of a multi-rank step (bucket hooks fired from the explicit backward, eager micro-step, one all-reduce per
         # bucket) on a process group of ANY size, including 1 -- what rank 0 of an 8-GPU run executes minus the wire time (bench.py --ddp-path)
         self.ddp_path = (self.world > 1 or (force_ddp_path and dist.is_available() and dist.is_initialized())) and hasattr(model, "grad_buckets")
@@ -449,6 +475,29 @@ class Trainer:
         ops.WEIGHTS_EPOCH += 1                           # caches keyed on (flat_param._version, WEIGHTS_EPOCH): transposed weights, packed operands
         self.model.weights_changed()
 
+    # ---- masked fine-tune (actprune.PruneMask) ----------------------------------------------------------------------------------------------
+    def _keep_init(self):
+        """The pruned rows of the weights, of both Adam moments and of the EMA shadow are set to +0.0 once, one launch each.  From then on every
+        optimiser step zeroes those rows of flat_grad before the norm (so the clip norm excludes them), and that alone keeps them: with a zero
+        gradient and zero moments Adam's update is m = b1 * 0 + (1 - b1) * 0 = 0, v = 0, p = 0 - lr * 0 / (sqrt(0) + eps) = +0.0 exactly, and
+        the shadow moves by (0 - 0) * (1 - decay) = 0 -- the rows stay +0.0 bit for bit with no second launch."""
+        from .anp import neuron_table
+        m = self.model
+        tab = neuron_table(m, "all")
+        keep = self.keep_pruned.keep
+        if not torch.is_tensor(keep) or keep.dim() != 1 or keep.numel() != tab.n_neurons:
+            raise ValueError(f"Trainer: keep_pruned holds {keep.numel() if torch.is_tensor(keep) else '?'} entries; the model has "
+                             f"{tab.n_neurons} neurons (anp.neuron_table(model, 'all'))")
+        self._keep_tab = tab
+        self._keep = keep.detach().to(m.flat_param.device, torch.float32).contiguous()
+        for buf in (m.flat_param, self.opt.exp_avg, self.opt.exp_avg_sq) + ((self.opt.ema,) if self.opt.ema is not None else ()):
+            ops.neuron_keep_rows(buf, tab, self._keep)
+        ops.WEIGHTS_EPOCH += 1                           # a raw-pointer write of the weights (as in `_swap_ema`)
+        m.weights_changed()
+
+    def _keep_grad(self):
+        ops.neuron_keep_rows(self.model.flat_grad, self._keep_tab, self._keep)
+
     # ---- sharpness-aware minimisation ------------------------------------------------------------------------------------------------------
     def _sam_init(self):
         """The buffers of a SAM step, allocated once: the backup of the weights, the norm word and, in "neuron" mode, the table and three floats
@@ -536,6 +585,7 @@ class Trainer:
             loss = self._sam_micro_step(batch, timesteps, noise, target_key, poison_key)
         else:
             loss = self._graphed(batch, timesteps, noise, target_key, poison_key)
+        masked = self._keep is not None and loss is not None      # a replayed micro-step ends with the mask launch: flat_grad is masked already
         if loss is None:
             loss = self.loss_fn.p_loss_by_keys(batch, self.model, target_latent_key=target_key, poison_latent_key=poison_key,
                                                timesteps=timesteps, noise=noise)
@@ -550,6 +600,8 @@ class Trainer:
             else:
                 allreduce_flat_grad(self.model.flat_grad, self.n_buckets, even_alone=self.ddp_path)
             self._sync_now = False
+            if self._keep is not None and not masked:
+                self._keep_grad()                                 # before the norm: the clip norm excludes the pruned rows
             self.opt.step(lr=self.lr, grad_inv_scale=1.0 / (self.world * self._step_scale), need_norm=self._step_scale != 1.0)
             self.sched_step += 1
             self._check_scale()
@@ -591,12 +643,19 @@ class Trainer:
             sd["lora"] = self.adapter.train_state()
         if self.sam is not None:
             sd["sam"] = asdict(self.sam)                 # for information only: SAM keeps no state between steps, load_state_dict ignores it
+        if self.keep_pruned is not None:
+            sd["keep_pruned"] = self.keep_pruned.keep.detach().to("cpu", torch.float32).clone()
         return sd
 
     def load_state_dict(self, sd: Dict):
         if ("lora" in sd) != (self.adapter is not None):
             raise ValueError("load_state_dict: the state " + ("holds a" if "lora" in sd else "holds no") + " LoRA adapter but this trainer was "
                              "built " + ("without" if "lora" in sd else "with") + " one (Trainer lora=...)")
+        if ("keep_pruned" in sd) != (self.keep_pruned is not None):
+            raise ValueError("load_state_dict: the state " + ("holds a" if "keep_pruned" in sd else "holds no") + " prune mask but this trainer was "
+                             "built " + ("without" if "keep_pruned" in sd else "with") + " one (Trainer keep_pruned=...)")
+        if self.keep_pruned is not None and not torch.equal(sd["keep_pruned"].to("cpu", torch.float32), self.keep_pruned.keep.to("cpu", torch.float32)):
+            raise ValueError("load_state_dict: the state was written under a different prune mask than this trainer's keep_pruned")
         if self.adapter is not None:
             self.adapter.load_train_state(sd["lora"])
         self.opt.load_state_dict(sd["optimizer"])
