@@ -45,12 +45,15 @@ IGNORE_ARGS = {"overwrite", "is_save_all_model_epochs", "R_trigger_only"}
 # args.json), --snr_gamma / --poison_loss_weight / --log_loss_split (train modes: the shaped loss, villandiffusion_amd.loss.LossFn snr_gamma /
 # poison_weight / track_split; resume takes them from args.json), --sam_rho / --sam_mode / --sam_eta / --sam_layers (train modes: sharpness-aware
 # steps, villandiffusion_amd.trainer.SAMConfig; resume takes them from args.json), --keep_pruned (train modes: a prune_mask.pt of
-# tools/fine_prune.py whose rows the fine-tune holds at zero, Trainer(keep_pruned=...); resume takes it from args.json).
+# tools/fine_prune.py whose rows the fine-tune holds at zero, Trainer(keep_pruned=...); resume takes it from args.json), --anchor_lambda /
+# --anchor_fisher / --anchor_ckpt (train modes: the L2-SP or, with a fisher.pt of tools/estimate_fisher.py, EWC penalty toward the weights of
+# --anchor_ckpt, villandiffusion_amd.anchor.AnchorConfig; --anchor_ckpt defaults to --ckpt and is recorded; resume takes them from args.json).
 # At their defaults they are left out of the JSON side files, which then read as they did before the options existed.
 EXTRA_MODE_OPTS = {MODE_SAMPLING: {"use_ema"}, MODE_MEASURE: {"use_ema"}}
 EXTRA_DEFAULTS = {"ema_decay": None, "use_ema": False, "lora_r": None, "lora_alpha": None, "lora_target": "attn", "lora_backward": None,
                   "snr_gamma": None, "poison_loss_weight": 1.0, "log_loss_split": False,
-                  "sam_rho": None, "sam_mode": None, "sam_eta": None, "sam_layers": None, "keep_pruned": None}
+                  "sam_rho": None, "sam_mode": None, "sam_eta": None, "sam_layers": None, "keep_pruned": None,
+                  "anchor_lambda": None, "anchor_fisher": None, "anchor_ckpt": None}
 
 
 def _side_file(d: dict) -> dict:
@@ -97,6 +100,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     a("--sam_layers", type=str, choices=["conv", "all"])
     # not in the reference: hold the rows a prune mask names (tools/fine_prune.py writes prune_mask.pt) at zero through the fine-tune
     a("--keep_pruned", type=str)
+    # not in the reference: hold the weights to those of --anchor_ckpt (default: --ckpt) with an L2-SP penalty, or EWC with --anchor_fisher FILE
+    a("--anchor_lambda", type=float); a("--anchor_fisher", type=str); a("--anchor_ckpt", type=str)
     return p.parse_args(argv)
 
 
@@ -122,6 +127,7 @@ class TrainingConfig:
     snr_gamma: Optional[float] = None; poison_loss_weight: float = 1.0; log_loss_split: bool = False
     sam_rho: Optional[float] = None; sam_mode: Optional[str] = None; sam_eta: Optional[float] = None; sam_layers: Optional[str] = None
     keep_pruned: Optional[str] = None
+    anchor_lambda: Optional[float] = None; anchor_fisher: Optional[str] = None; anchor_ckpt: Optional[str] = None
     extra: dict = field(default_factory=dict)
 
 
@@ -188,6 +194,9 @@ def setup(args: argparse.Namespace, preflight: bool = False) -> TrainingConfig:
     cfg.gradient_accumulation_steps = int(bs // cfg.batch)
     sam_config(cfg)                                                    # ValueError / NotImplementedError before anything is created
     keep_pruned_mask(cfg)
+    anchor_settings(cfg)
+    if mode in (MODE_TRAIN, MODE_TRAIN_MEASURE) and cfg.anchor_lambda is not None:
+        args.anchor_ckpt = cfg.anchor_ckpt                             # the default (--ckpt) is recorded: a resume anchors to the original start
     # One process per GPU (torchrun): every rank computes the same config, but the existing-directory check, the directory
     # creation and the JSON side files belong to rank 0 alone -- main() puts a barrier behind it.  (The reference is a single
     # process driving nn.DataParallel, :440, so it has no such distinction.)
@@ -266,6 +275,51 @@ def keep_pruned_mask(cfg: TrainingConfig):
     world = max(len(str(cfg.gpu).split(",")), int(os.environ.get("WORLD_SIZE", "1")))
     check_keep_pruned(mask, lora=cfg.lora_r, sam=cfg.sam_rho, world=world)
     return mask
+
+
+def anchor_settings(cfg: TrainingConfig):
+    """Checks --anchor_lambda / --anchor_fisher / --anchor_ckpt and fills the default of --anchor_ckpt (the run's --ckpt).  -> the AnchorConfig
+    mode ("l2sp" / "ewc"), or None without --anchor_lambda.  In the train modes it raises what Trainer would for the combinations an anchored
+    fine-tune is not built with (LoRA, more than one GPU, the f16 mode), before a device is touched; the Fisher itself is read in train_loop."""
+    if cfg.anchor_lambda is None:
+        if cfg.anchor_fisher is not None or cfg.anchor_ckpt is not None:
+            raise ValueError("--anchor_fisher / --anchor_ckpt need --anchor_lambda")
+        return None
+    from villandiffusion_amd.anchor import FISHER_FILE, AnchorConfig, check_anchor
+    ac = AnchorConfig(lam=cfg.anchor_lambda)                           # ValueError for a lambda that is not positive and finite
+    if cfg.mode in (MODE_TRAIN, MODE_RESUME, MODE_TRAIN_MEASURE):
+        if cfg.anchor_ckpt is None:
+            if cfg.ckpt is None or cfg.mode == MODE_RESUME:
+                raise ValueError("--anchor_lambda needs a checkpoint to hold the weights to: give --ckpt or --anchor_ckpt (a run from scratch has "
+                                 "no start a resume could reload)")
+            cfg.anchor_ckpt = cfg.ckpt
+        if cfg.anchor_fisher is not None:
+            f = cfg.anchor_fisher
+            if not os.path.isfile(os.path.join(f, FISHER_FILE) if os.path.isdir(f) else f):
+                raise FileNotFoundError(f"--anchor_fisher {f}: no such file (tools/estimate_fisher.py writes fisher.pt)")
+        world = max(len(str(cfg.gpu).split(",")), int(os.environ.get("WORLD_SIZE", "1")))
+        check_anchor(ac, lora=cfg.lora_r, world=world, conv_math="f16" if getattr(cfg, "mixed_precision", "no") == "fp16" else None)
+    return "ewc" if cfg.anchor_fisher is not None else "l2sp"
+
+
+def anchor_config(cfg: TrainingConfig, model, dsl):
+    """(AnchorConfig, anchor_weights) for Trainer, or (None, None): the Fisher from --anchor_fisher (checked against the model's layout) and w0,
+    the flat weights of --anchor_ckpt -- the model's own where that is the checkpoint it was just built from."""
+    mode = anchor_settings(cfg)
+    if mode is None:
+        return None, None
+    from model import DiffuserModelSched
+    from villandiffusion_amd.anchor import AnchorConfig, load_fisher
+    fisher = load_fisher(cfg.anchor_fisher, model) if mode == "ewc" else None
+    w0 = None
+    if cfg.mode == MODE_RESUME or cfg.anchor_ckpt != cfg.ckpt:
+        start = DiffuserModelSched.get_model_sched(image_size=dsl.image_size, channels=dsl.channel, ckpt=cfg.anchor_ckpt, sde_type=cfg.sde_type,
+                                                   clip_sample=cfg.clip, noise_sched_type=cfg.sched)[0]
+        if start.flat_numel != model.flat_numel:
+            raise ValueError(f"--anchor_ckpt {cfg.anchor_ckpt}: its network has {start.flat_numel} floats, the run's has {model.flat_numel}")
+        w0 = start.flat_param.detach().clone()
+        del start
+    return AnchorConfig(lam=cfg.anchor_lambda, mode=mode, fisher=fisher), w0
 
 
 def loss_shaping(cfg: TrainingConfig) -> dict:
@@ -574,10 +628,11 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
     if loss_fn.shaped:
         dsl.batch_flags = True                                         # the lean training batches carry `is_clean` for the shaped loss
     n_batch = (len(dsl) + cfg.batch * world - 1) // (cfg.batch * world)
+    anchor, anchor_w0 = anchor_config(cfg, model, dsl)
     trainer = Trainer(model, loss_fn, lr=cfg.learning_rate, total_steps=n_batch * cfg.epoch, warmup_steps=cfg.lr_warmup_steps,
                       grad_accum=cfg.gradient_accumulation_steps, ema=EMAConfig(decay=cfg.ema_decay) if cfg.ema_decay is not None else None,
                       lora=lora_config(cfg), lora_backward=cfg.lora_backward, sam=sam_config(cfg),
-                      keep_pruned=keep_pruned_mask(cfg))
+                      keep_pruned=keep_pruned_mask(cfg), anchor=anchor, anchor_weights=anchor_w0)
     start_epoch, step = 0, 0
     if cfg.mode == MODE_RESUME:
         trainer.load_state_dict(torch.load(os.path.join(cfg.ckpt_path, "trainer.pt"), map_location=model.device))
@@ -608,7 +663,8 @@ def train_loop(cfg: TrainingConfig, dsl, rank: int, world: int):
                 if split_acc is not None:
                     split = split_fields(split_acc.tolist())
                     split_acc.zero_()
-                print(f"epoch {epoch} step {step} loss {float(loss):.5f} lr {trainer.lr:.3e}{split}", flush=True)
+                pen = f" anchor_pen {trainer.anchor_penalty:.5e}" if trainer.anchor is not None else ""      # (read where a line is printed)
+                print(f"epoch {epoch} step {step} loss {float(loss):.5f} lr {trainer.lr:.3e}{split}{pen}", flush=True)
         if rank == 0:
             if (epoch + 1) % cfg.save_image_epochs == 0 or epoch == cfg.epoch - 1:
                 with sampling_weights():
@@ -695,6 +751,8 @@ def apply_gpu_flag(args: argparse.Namespace, argv: Optional[List[str]]):
         raise NotImplementedError("--sam_rho on more than one GPU is not built")
     if getattr(args, "keep_pruned", None) is not None:
         raise NotImplementedError("--keep_pruned on more than one GPU is not built")
+    if getattr(args, "anchor_lambda", None) is not None:
+        raise NotImplementedError("--anchor_lambda on more than one GPU is not built")
     import socket
     import subprocess
     with socket.socket() as sk:

@@ -614,6 +614,30 @@ int vd_channel_stats(const int64_t* host_table, const int64_t* table, int n_jobs
  * vd_neuron_scale's layout (one wave per row; an aligned row moves as f32x4, any other as scalars).  Every other float of buf -- kept rows,
  * biases, floats outside the table -- is neither read nor written.  One launch for the network. */
 int vd_neuron_keep_rows(float* buf, const int64_t* table, int n_jobs, int64_t total_blocks, const float* keep, void* stream);
+/* Anchored fine-tuning (anchor.py, Trainer(anchor=...)) -- csrc/vd_anchor.hip: the penalty lambda / 2 * sum_i F_i (w_i - w0_i)^2 that holds the
+ * weights to a starting point w0 (EWC, Kirkpatrick et al. 2017, F the diagonal Fisher information; F = 1: L2-SP, Li et al. 2018).  Plain C++ with
+ * vector loads and stores, no atomics, every operation rounded on its own (no FMA contraction), every sum in a fixed order: bit-reproducible.
+ * Both kernels walk the n floats as vd_sam_perturb does: items of four from the buffer's start, item q in thread q % (grid * block), one 16-byte
+ * access where every pointer is 16-byte aligned, four scalar ones otherwise (and for a last, partial item), with the same values and the same
+ * sums either way.  Pointers are 4-byte aligned.  VD_EINVAL before any launch: n < 0, a required pointer that is NULL, buffers that overlap, a
+ * non-finite s or coef, a negative s.
+ *
+ * vd_anchor_plan (host only): the launch shape of both kernels for n floats.  It is vd_sam_plan's rule:
+ *   block = 256, floats_per_thread = 16, grid = clamp(ceil(n / (block * floats_per_thread)), 1, 1024); past the cap a thread strides on. */
+int vd_anchor_plan(int64_t n, int* grid, int* block, int* floats_per_thread);
+/* One step of the Fisher estimate, in this order:  q = g[i] * g[i];  F[i] = F[i] + s * q.   s >= 0 is the 1 / K of a mean over K batches.
+ * F and g do not overlap.  12 B/float. */
+int vd_fisher_accum(float* F, const float* g, int64_t n, float s, void* stream);
+/* The penalty's gradient added to g, in this order:  d = w[i] - w0[i];  t = F[i] * d (F NULL: t = d, L2-SP);  g[i] = g[i] + coef * t.
+ * With pen != NULL the same pass forms *pen = sum_i t * d (a device word: the UNSCALED penalty sum F d^2; the caller multiplies by lambda / 2),
+ * every product t * d rounded to f32 and added in vd_sam_norm_sq's two stages:
+ *   1. a thread keeps one f32 partial per position k % 4 over its items in ascending order, adds them as (a0 + a1) + (a2 + a3); the 64 lanes
+ *      of a wave are added by a fixed xor tree, the four waves as (r0 + r1) + (r2 + r3); partial[workgroup] holds the result;
+ *   2. one workgroup: thread t adds partial[t], partial[t + 256], ... in that order, then the same tree.
+ * The longest chain of additions is ceil(ceil(n / 4) / (grid * block)) + ceil(grid / 256) + 18.
+ * partial: >= 1024 floats of scratch, needed with pen only.  pen NULL: no sum is formed, neither partial nor pen is touched.  w, w0 and F are
+ * read only; g, w, w0, F do not overlap each other or the scratch.  20 B/float (16 without F). */
+int vd_anchor_grad(float* g, const float* w, const float* w0, const float* F, int64_t n, float coef, float* partial, float* pen, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10 -- sampler steps (diffusers *Scheduler.step, via pipeline(...) VillanDiffusion.py:579).

@@ -6,7 +6,9 @@ rate for the model's size (2e-4 up to 64 x 64, 6e-5 above).  VP-type UNet2DModel
 whose network is an NCSNppModel (SDE-VE, ScoreSdeVeScheduler) goes to villandiffusion_amd.defense_ve: the trigger is in noise units, the loss
 terms are in noise-prediction units at sigma_T, the record gains "sigma".  A checkpoint directory with a vqvae/ folder (latent diffusion) goes to
 villandiffusion_amd.defense_ldm: --trigger is latent-shaped or pixel-shaped (encoded once; the record gains "space"), the latent UNet alone is
-fine-tuned and the VQ-VAE is written back as it was."""
+fine-tuned and the VQ-VAE is written back as it was.  --anchor_lambda L [--anchor_fisher fisher.pt] holds the weights to the checkpoint's with
+the L2-SP (or, with a Fisher of tools/estimate_fisher.py, the EWC) penalty of villandiffusion_amd.anchor; the record gains "anchor_lambda" and
+"anchor_penalty", the penalty at the start of every step."""
 import argparse
 import json
 import os
@@ -26,7 +28,11 @@ def main(argv=None):
     ap.add_argument("--w-shift", type=float, default=1.0, help="weight of mse(model(eps + trigger), frozen(eps))")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", required=True, help="output directory of the repaired checkpoint")
+    ap.add_argument("--anchor_lambda", type=float, default=None, help="weight of the penalty toward the checkpoint's weights (default: none)")
+    ap.add_argument("--anchor_fisher", default=None, help="a fisher.pt of tools/estimate_fisher.py: EWC instead of L2-SP")
     args = ap.parse_args(argv)
+    if args.anchor_fisher is not None and args.anchor_lambda is None:
+        ap.error("--anchor_fisher needs --anchor_lambda")
 
     import torch
     from villandiffusion_amd.ncsnpp import NCSNppModel
@@ -36,6 +42,9 @@ def main(argv=None):
     tau = torch.load(args.trigger, map_location="cpu")
     lr = args.lr if args.lr is not None else (2e-4 if int(pipe.unet.sample_size) <= 64 else 6e-5)
     kw = dict(steps=args.steps, batch=args.batch, lr=lr, w_clean=args.w_clean, w_shift=args.w_shift, seed=args.seed)
+    if args.anchor_lambda is not None:
+        from villandiffusion_amd.anchor import load_fisher
+        kw.update(anchor_lambda=args.anchor_lambda, fisher=None if args.anchor_fisher is None else load_fisher(args.anchor_fisher, pipe.unet))
     space = None
     if os.path.isdir(os.path.join(args.ckpt, "vqvae")):
         from villandiffusion_amd import defense_ldm
@@ -52,7 +61,9 @@ def main(argv=None):
     info = {"ckpt": os.path.abspath(args.ckpt), "trigger": os.path.abspath(args.trigger), "steps": res.steps, "batch": res.batch, "lr": res.lr,
             "w_clean": res.w_clean, "w_shift": res.w_shift, "max_grad_norm": res.max_grad_norm, "seed": res.seed, "timestep": res.timestep,
             "total": res.total, "clean": res.clean, "shift": res.shift} | ({"sigma": res.sigma} if res.sigma is not None else {}) | \
-        ({"space": space} if space is not None else {})
+        ({"space": space} if space is not None else {}) | \
+        ({"anchor_lambda": res.anchor_lambda, "anchor_fisher": None if args.anchor_fisher is None else os.path.abspath(args.anchor_fisher),
+          "anchor_penalty": res.anchor_penalty} if res.anchor_penalty is not None else {})
     with open(os.path.join(args.out, "removal.json"), "w") as f:
         json.dump(info, f, indent=1)
     print(json.dumps({k: info[k] for k in ("steps", "batch", "lr", "timestep")} | {"shift_first": res.shift[0], "shift_last": res.shift[-1],

@@ -338,7 +338,8 @@ def backdoor_features(pipeline, trigger: torch.Tensor, *, n: int, batch: int, nu
 # ------------------------------------------------------------------------------------------------------------------------------ removal
 def remove_backdoor(pipeline, trigger: torch.Tensor, *, steps: int, batch: int, lr: float, w_clean: float = 1.0, w_shift: float = 1.0,
                     max_grad_norm: Optional[float] = 1.0, seed: int = 0, timestep: Optional[int] = None,
-                    noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None) -> BackdoorRemoval:
+                    noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None, anchor_lambda: Optional[float] = None,
+                    fisher: Optional[torch.Tensor] = None) -> BackdoorRemoval:
     """`mitigation.remove_backdoor(pipeline.unet, pipeline.scheduler, tau, ...)` at tau = the trigger in latent space (a pixel-shaped trigger is
     encoded once): the latent UNet is fine-tuned IN PLACE, the curves and the weights afterwards are that call's.  The VQ-VAE is untouched."""
     # everything that can be checked is checked before the device is touched (a pixel trigger is encoded on the device)
@@ -347,6 +348,7 @@ def remove_backdoor(pipeline, trigger: torch.Tensor, *, steps: int, batch: int, 
     unet, sched = pipeline.unet, pipeline.scheduler
     _check_removal_args("remove_backdoor", float(w_clean), float(w_shift), max_grad_norm)
     _check_f16("remove_backdoor", unet)
+    mitigation._anchor_args("remove_backdoor", unet, anchor_lambda, fisher)
     _check_loop_args("remove_backdoor", unet, steps, batch, float(lr), noise, _shape(unet))
     _vp_timestep("remove_backdoor", sched, timestep)
     if space == "pixel":
@@ -354,4 +356,5 @@ def remove_backdoor(pipeline, trigger: torch.Tensor, *, steps: int, batch: int, 
         lib.require_device()
     tau = _latent(pipeline, trigger, space) if space == "pixel" else trigger
     return mitigation.remove_backdoor(unet, sched, tau, steps=steps, batch=batch, lr=lr, w_clean=w_clean,
-                                      w_shift=w_shift, max_grad_norm=max_grad_norm, seed=seed, timestep=timestep, noise=noise)
+                                      w_shift=w_shift, max_grad_norm=max_grad_norm, seed=seed, timestep=timestep, noise=noise,
+                                      **({} if anchor_lambda is None else dict(anchor_lambda=anchor_lambda, fisher=fisher)))

@@ -214,11 +214,13 @@ def removal_objective(model, frozen, tau: torch.Tensor, eps: torch.Tensor, sigma
 
 def remove_backdoor(model, noise_sched, trigger: torch.Tensor, *, steps: int, batch: int, lr: float, w_clean: float = 1.0, w_shift: float = 1.0,
                     max_grad_norm: Optional[float] = 1.0, seed: int = 0, timestep: Optional[int] = None,
-                    noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None) -> BackdoorRemoval:
+                    noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None, anchor_lambda: Optional[float] = None,
+                    fisher: Optional[torch.Tensor] = None) -> BackdoorRemoval:
     """Fine-tune `model` IN PLACE for `steps` Adam(lr, constant) iterations of the removal loss (noise-prediction units, see removal_objective)
     on `batch` unit-variance noise images each, at the noise level of `timestep` (default sigma_T), against a frozen copy of its state at entry
     (returned as `.frozen`, never written).  The loop is `mitigation._run_removal`: clip + FusedAdam, the three terms of every step read once
-    after the loop (clean / shift scaled by sigma^2 there).  `time_proj.weight`, the fixed Fourier features, is never unfrozen or written."""
+    after the loop (clean / shift scaled by sigma^2 there).  `time_proj.weight`, the fixed Fourier features, is never unfrozen or written.
+    anchor_lambda / fisher: as in `mitigation.remove_backdoor` (the penalty is not scaled by sigma)."""
     # everything that can be checked is checked before the device is touched (in _run_removal)
     lr, w_clean, w_shift = float(lr), float(w_clean), float(w_shift)
     _check_removal_args("remove_backdoor", w_clean, w_shift, max_grad_norm)
@@ -229,8 +231,12 @@ def remove_backdoor(model, noise_sched, trigger: torch.Tensor, *, steps: int, ba
     T, sigma = _sigma_at(sched, timestep, "remove_backdoor")
     _check_trigger("remove_backdoor", trigger, shape)
     s2 = sigma * sigma
-    frozen, host = _run_removal("remove_backdoor", model, _teacher, trigger, shape, sigma, w_clean * s2, w_shift * s2, lr, max_grad_norm, steps,
-                                batch, seed, noise, prepare=lambda x: _scaled(x, sigma), skip=(model.time_proj.weight,))
+    from .mitigation import _anchor_args
+    _anchor_args("remove_backdoor", model, anchor_lambda, fisher)
+    akw = {} if anchor_lambda is None else dict(anchor_lambda=anchor_lambda, fisher=fisher)
+    frozen, host, *pen = _run_removal("remove_backdoor", model, _teacher, trigger, shape, sigma, w_clean * s2, w_shift * s2, lr, max_grad_norm, steps,
+                                      batch, seed, noise, prepare=lambda x: _scaled(x, sigma), skip=(model.time_proj.weight,), **akw)
     return BackdoorRemoval(total=[r[0] for r in host], clean=[r[1] * s2 for r in host], shift=[r[2] * s2 for r in host], frozen=frozen, lr=lr,
                            steps=steps, batch=batch, w_clean=w_clean, w_shift=w_shift, max_grad_norm=max_grad_norm, timestep=T, seed=int(seed),
-                           sigma=sigma)                    # (the VE record carries the noise level of the fine-tune)
+                           sigma=sigma,                    # (the VE record carries the noise level of the fine-tune)
+                           **({} if not pen else dict(anchor_penalty=pen[0], anchor_lambda=float(anchor_lambda))))

@@ -198,6 +198,8 @@ class BackdoorRemoval:
     timestep: int
     seed: int
     sigma: Optional[float] = None          # SDE-VE (`defense_ve`) only: the noise level of the fine-tune
+    anchor_penalty: Optional[List[float]] = None      # with anchor_lambda only: per step, at its START, lambda / 2 * sum F (w - w0)^2 (0 at step one)
+    anchor_lambda: Optional[float] = None
 
 
 def _frozen_copy(model):
@@ -234,9 +236,14 @@ def _removal_into(model, teacher, tau, eps, t2, w_clean, w_shift, terms, partial
     return terms
 
 
-def _removal_step(model, teacher, opt, tau, eps, t2, w_clean, w_shift, terms, partial):
-    """One step of `remove_backdoor`'s loop: the evaluation into `terms`, clip + Adam, the gradient reset."""
+def _removal_step(model, teacher, opt, tau, eps, t2, w_clean, w_shift, terms, partial, anchor=None):
+    """One step of `remove_backdoor`'s loop: the evaluation into `terms`, clip + Adam, the gradient reset.  anchor: None, or (w0, F or None,
+    lambda, a 1024-float scratch, the device word of this step's unscaled penalty) -- one launch adds lambda * F * (w - w0) to the gradient before
+    the clip (anchor.py)."""
     _removal_into(model, teacher, tau, eps, t2, w_clean, w_shift, terms, partial)
+    if anchor is not None:
+        w0, F, lam, scratch, pen = anchor
+        ops.anchor_grad(model.flat_grad, model.flat_param, w0, F, lam, scratch, pen)
     opt.step()
     model.zero_grad()
 
@@ -254,12 +261,28 @@ def _check_f16(what, model):
         raise NotImplementedError(f"{what}: conv_math 'f16' needs loss scaling, which the removal loop does not have; use 'bf16x3', 'f32' or 'bf16'")
 
 
+def _anchor_args(what, model, anchor_lambda, fisher):
+    """The AnchorConfig of a removal loop's anchor_lambda / fisher (None, None: no anchor); every refusal before the device is touched."""
+    if anchor_lambda is None:
+        if fisher is not None:
+            raise ValueError(f"{what}: fisher needs anchor_lambda")
+        return None
+    from .anchor import AnchorConfig
+    cfg = AnchorConfig(lam=anchor_lambda, mode="l2sp" if fisher is None else "ewc", fisher=fisher)
+    if fisher is not None and fisher.numel() != model.flat_numel:
+        raise ValueError(f"{what}: the Fisher holds {fisher.numel()} entries; the model's flat_param has {model.flat_numel} floats")
+    return cfg
+
+
 def _run_removal(what, model, make_teacher, trigger, shape, t, w_clean, w_shift, lr, max_grad_norm, steps, batch, seed, noise,
-                 prepare=lambda x: x, skip=()):
+                 prepare=lambda x: x, skip=(), anchor_lambda=None, fisher=None):
     """The removal loop of both families: `steps` iterations of clip + FusedAdam(lr) on `model`, in place, at the noise level `t`, against a
     frozen copy of its state at entry.  make_teacher: frozen copy -> (x, t -> its output), called once before the loop with the model's
     parameters already trainable.  prepare: what turns the trigger and each iteration's unit noise into network input units (SDE-VE scales by
-    sigma).  skip: parameters that are never unfrozen.  -> (the frozen copy, the [total, clean, shift] rows of every step, on the host)"""
+    sigma).  skip: parameters that are never unfrozen.  -> (the frozen copy, the [total, clean, shift] rows of every step, on the host)
+    anchor_lambda (with fisher: EWC, else L2-SP): every step's gradient gains lambda * F * (w - w0), w0 the frozen copy's flat_param, and a third
+    value is returned: the penalty lambda / 2 * sum F (w - w0)^2 at the start of every step.  At the defaults nothing changes."""
+    acfg = _anchor_args(what, model, anchor_lambda, fisher)
     from . import lib
     from .trainer import FusedAdam
     lib.require_device()                                   # VillanHipError without an MI355X: there is no fallback
@@ -272,12 +295,21 @@ def _run_removal(what, model, make_teacher, trigger, shape, t, w_clean, w_shift,
     t2 = torch.full((2 * batch,), float(t), device=dev, dtype=torch.float32)
     eps_buf = torch.empty((batch,) + shape, device=dev, dtype=torch.float32)
     per_iter = (eps_buf.numel() + 3) // 4                  # Philox counters one iteration's noise consumes (four normals each)
+    pens = anchor_of = None
+    if acfg is not None:
+        pens = torch.zeros(steps, device=dev, dtype=torch.float32)
+        F = None if acfg.fisher is None else acfg.fisher.detach().to(dev, torch.float32).contiguous()
+        scratch = torch.empty(1024, device=dev, dtype=torch.float32)
+        anchor_of = lambda it: (frozen.flat_param, F, float(acfg.lam), scratch, pens[it:it + 1])
     with _trainable(model, skip):                          # the fine-tune trains every parameter (but `skip`); the caller's flags come back on exit
         teacher = make_teacher(frozen)                     # before the loop: a captured forward synchronises
         model.zero_grad()
         for it in range(steps):
             eps = prepare(_noise_of(what, noise, it, eps_buf, seed, per_iter, dev))
-            _removal_step(model, teacher, opt, tau, eps, t2, w_clean, w_shift, curves[it], partial)
+            _removal_step(model, teacher, opt, tau, eps, t2, w_clean, w_shift, curves[it], partial,
+                          **({} if anchor_of is None else {"anchor": anchor_of(it)}))
+    if pens is not None:
+        return frozen, curves.cpu().tolist(), [0.5 * float(acfg.lam) * v for v in pens.cpu().tolist()]
     return frozen, curves.cpu().tolist()                   # the one read of the loop's results
 
 
@@ -318,9 +350,11 @@ def removal_objective(model, frozen, tau: torch.Tensor, eps: torch.Tensor, t, w_
 
 def remove_backdoor(model, noise_sched, trigger: torch.Tensor, *, steps: int, batch: int, lr: float, w_clean: float = 1.0, w_shift: float = 1.0,
                     max_grad_norm: Optional[float] = 1.0, seed: int = 0, timestep: Optional[int] = None,
-                    noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None) -> BackdoorRemoval:
+                    noise: Union[None, torch.Tensor, Callable[[int], torch.Tensor]] = None, anchor_lambda: Optional[float] = None,
+                    fisher: Optional[torch.Tensor] = None) -> BackdoorRemoval:
     """Fine-tune `model` IN PLACE for `steps` Adam(lr, constant) iterations of the removal loss on `batch` noise images each, against a frozen copy
-    of its state at entry (returned as `.frozen`, never written).
+    of its state at entry (returned as `.frozen`, never written).  anchor_lambda: the weights are held to that state by the L2-SP penalty, or with
+    `fisher` (a flat Fisher, anchor.estimate_fisher) the EWC penalty; the record gains `anchor_penalty`, its value at the start of every step.
 
     timestep: defaults to the scheduler's last training timestep.  noise: None -- fresh per iteration from the device Philox stream (seed, disjoint
     counter ranges per iteration); a [steps, batch, C, H, W] tensor or a callable iteration -> [batch, C, H, W] makes a run reproducible against
@@ -335,7 +369,10 @@ def remove_backdoor(model, noise_sched, trigger: torch.Tensor, *, steps: int, ba
     T = _vp_timestep("remove_backdoor", noise_sched, timestep)
     _check_trigger("remove_backdoor", trigger, shape)
     from .pipelines import sampler_forward
-    frozen, host = _run_removal("remove_backdoor", model, lambda twin: sampler_forward(twin, batch), trigger, shape, T, w_clean, w_shift, lr,
-                                max_grad_norm, steps, batch, seed, noise)
+    _anchor_args("remove_backdoor", model, anchor_lambda, fisher)
+    akw = {} if anchor_lambda is None else dict(anchor_lambda=anchor_lambda, fisher=fisher)
+    frozen, host, *pen = _run_removal("remove_backdoor", model, lambda twin: sampler_forward(twin, batch), trigger, shape, T, w_clean, w_shift, lr,
+                                      max_grad_norm, steps, batch, seed, noise, **akw)
     return BackdoorRemoval(total=[r[0] for r in host], clean=[r[1] for r in host], shift=[r[2] for r in host], frozen=frozen, lr=lr, steps=steps,
-                           batch=batch, w_clean=w_clean, w_shift=w_shift, max_grad_norm=max_grad_norm, timestep=T, seed=int(seed))
+                           batch=batch, w_clean=w_clean, w_shift=w_shift, max_grad_norm=max_grad_norm, timestep=T, seed=int(seed),
+                           **({} if not pen else dict(anchor_penalty=pen[0], anchor_lambda=float(anchor_lambda))))

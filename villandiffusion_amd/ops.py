@@ -1376,6 +1376,33 @@ def neuron_axpy(w, g, tab, coef):
     return w
 
 
+def anchor_plan(n: int):
+    """(grid, block, floats per thread) of vd_fisher_accum and vd_anchor_grad for n floats: asked of the library on the host."""
+    g, b, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    L.check(L.load().vd_anchor_plan(int(n), C.byref(g), C.byref(b), C.byref(f)), "vd_anchor_plan")
+    return g.value, b.value, f.value
+
+
+def fisher_accum(F, g, s: float):
+    """F += s * (g * g), every operation rounded on its own (vd_fisher_accum: one pass).  s >= 0: the 1 / K of a mean over K batches."""
+    n = _sam_flat(F, g)
+    _timed("fisher_accum (fisher_accum_kernel)", 12.0 * n, "hbm", lambda: L.check(                       # F, g read; F written
+        _lib().vd_fisher_accum(_p(F), _p(g), n, float(s), _s()), "vd_fisher_accum"))
+    return F
+
+
+def anchor_grad(g, w, w0, F, coef: float, partial=None, pen=None):
+    """g += coef * t with d = w - w0 and t = F * d (F None: t = d, L2-SP), and in the same pass pen = sum t * d, the unscaled penalty, in
+    vd_sam_norm_sq's fixed order (pen None: no sum; vd_anchor_grad).  w, w0 and F are read only."""
+    n = _sam_flat(g, w, w0, F)
+    if pen is not None:
+        assert partial is not None and partial.numel() >= 1024 and partial.dtype == torch.float32 and pen.dtype == torch.float32
+    _timed("anchor_grad (anchor_grad_kernel)", 4.0 * n * (4 + (F is not None)), "hbm", lambda: L.check(  # g, w, w0 (, F) read; g written
+        _lib().vd_anchor_grad(_p(g), _p(w), _p(w0), _p(F), n, float(coef), _p(partial if pen is not None else None), _p(pen), _s()),
+        "vd_anchor_grad"))
+    return g
+
+
 CHANNEL_ACTS = {"raw": 0, "silu_gn": 1}
 CHANNEL_JOB_INTS = 11     # x, mean, rstd, gamma, beta, B, C, HW, G, first channel, first workgroup
 

@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .anchor import AnchorConfig, check_anchor
 from .schedulers import get_cosine_schedule_with_warmup_lambda
 
 
@@ -321,8 +322,11 @@ class Trainer:
     def __init__(self, model, loss_fn, lr: float, total_steps: int, warmup_steps: int = 500, grad_accum: int = 1,
                  max_grad_norm: Optional[float] = 1.0, n_allreduce_buckets: int = 4, graph_micro_step: Optional[bool] = None,
                  force_ddp_path: bool = False, ema: Optional[EMAConfig] = None, lora=None, lora_backward: Optional[str] = None,
-                 sam: Optional[SAMConfig] = None, keep_pruned=None):
-        """keep_pruned: an actprune.PruneMask holds the pruned weight rows at +0.0 through the fine-tune (`_keep_init`); None changes nothing.
+                 sam: Optional[SAMConfig] = None, keep_pruned=None, anchor: Optional[AnchorConfig] = None,
+                 anchor_weights: Optional[torch.Tensor] = None):
+        """anchor: an anchor.AnchorConfig adds the gradient of lam / 2 * sum F (w - w0)^2 to every optimiser step (`_anchor_init`); w0 is the
+        network's weights at construction, or `anchor_weights` (a flat tensor: a resumed run anchors to the original start); None changes nothing.
+        keep_pruned: an actprune.PruneMask holds the pruned weight rows at +0.0 through the fine-tune (`_keep_init`); None changes nothing.
         sam: a SAMConfig makes every optimiser step a sharpness-aware one (`_sam_micro_step`); None changes nothing.
         lora_backward (with lora only; None means "full"): "full" -- the backward forms every weight gradient; "adapted" -- only what the
         adapter needs (lora.BackwardRoute; UNet2DModel).  The mode belongs to the run: no state records it, a state of either loads in both."""
@@ -333,6 +337,10 @@ class Trainer:
                   getattr(model, "conv_math", None))              # every SAM refusal comes before the first launch
         self.sam = sam
         check_keep_pruned(keep_pruned, lora, sam, dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1)
+        check_anchor(anchor, lora, dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1,
+                     getattr(model, "conv_math", None))           # every anchor refusal comes before the first launch
+        if anchor is None and anchor_weights is not None:
+            raise ValueError("Trainer: anchor_weights needs anchor=AnchorConfig(...)")
         if lora is None and lora_backward is not None:
             raise ValueError(f"Trainer: lora_backward={lora_backward!r} needs lora=LoRAConfig(...)")
         if lora is not None:
@@ -379,6 +387,9 @@ class Trainer:
         self.keep_pruned, self._keep, self._keep_tab = keep_pruned, None, None
         if keep_pruned is not None:
             self._keep_init()
+        self.anchor = anchor
+        if anchor is not None:
+            self._anchor_init(anchor_weights)
         # force_ddp_path: the schedule of a multi-rank step (bucket hooks fired from the explicit backward, eager micro-step, one all-reduce per
         # bucket) on a process group of ANY size, including 1 -- what rank 0 of an 8-GPU run executes minus the wire time (bench.py --ddp-path)
         self.ddp_path = (self.world > 1 or (force_ddp_path and dist.is_available() and dist.is_initialized())) and hasattr(model, "grad_buckets")
@@ -498,6 +509,35 @@ class Trainer:
     def _keep_grad(self):
         ops.neuron_keep_rows(self.model.flat_grad, self._keep_tab, self._keep)
 
+    # ---- anchored fine-tune (anchor.AnchorConfig) ---------------------------------------------------------------------------------------------
+    def _anchor_init(self, anchor_weights):
+        """w0 (a clone of the weights as they are now -- after `_keep_init` zeroed pruned rows -- or the given flat tensor), the Fisher on the
+        device, the penalty word and the scratch of its sum, allocated once."""
+        fp = self.model.flat_param
+        for what, v in (("anchor_weights", anchor_weights), ("the anchor's fisher", self.anchor.fisher)):
+            if v is not None and (not torch.is_tensor(v) or v.dim() != 1 or v.numel() != fp.numel()):
+                raise ValueError(f"Trainer: {what} holds {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}; the model's flat_param has "
+                                 f"{fp.numel()} floats")
+        self._anchor_lam = float(self.anchor.lam)          # (what the launch reads)
+        self._anchor_w0 = (fp if anchor_weights is None else anchor_weights).detach().to(fp.device, torch.float32).clone().contiguous()
+        self._anchor_F = None if self.anchor.fisher is None else self.anchor.fisher.detach().to(fp.device, torch.float32).clone().contiguous()
+        self._anchor_pen = torch.zeros(1, device=fp.device, dtype=torch.float32)
+        self._anchor_partial = torch.empty(1024, device=fp.device, dtype=torch.float32)
+
+    def _anchor_grad(self):
+        """flat_grad += lam * F * (w - w0) and the unscaled penalty into its device word: one launch, nothing read back.  At a sync step
+        flat_grad holds the MEAN gradient of the accumulation window (the loss gradient is pre-divided by grad_accum), so coef = lam."""
+        m = self.model
+        ops.anchor_grad(m.flat_grad, m.flat_param, self._anchor_w0, self._anchor_F, self._anchor_lam, self._anchor_partial, self._anchor_pen)
+
+    @property
+    def anchor_penalty(self) -> Optional[float]:
+        """lam / 2 * sum F (w - w0)^2 at the weights the last optimiser step STARTED from (what the step's gradient saw); None without an
+        anchor.  Reading it synchronises; the step itself never does."""
+        if self.anchor is None:
+            return None
+        return 0.5 * self._anchor_lam * float(self._anchor_pen)
+
     # ---- sharpness-aware minimisation ------------------------------------------------------------------------------------------------------
     def _sam_init(self):
         """The buffers of a SAM step, allocated once: the backup of the weights, the norm word and, in "neuron" mode, the table and three floats
@@ -600,8 +640,11 @@ class Trainer:
             else:
                 allreduce_flat_grad(self.model.flat_grad, self.n_buckets, even_alone=self.ddp_path)
             self._sync_now = False
-            if self._keep is not None and not masked:
-                self._keep_grad()                                 # before the norm: the clip norm excludes the pruned rows
+            if self.anchor is not None:
+                self._anchor_grad()                               # before the norm: the clip sees the gradient of loss + penalty
+            if self._keep is not None and (not masked or self.anchor is not None):
+                self._keep_grad()                                 # before the norm: the clip norm excludes the pruned rows (whose w0 need not be 0:
+                                                                  # the anchor launch would pull them back, so the mask follows it at every sync)
             self.opt.step(lr=self.lr, grad_inv_scale=1.0 / (self.world * self._step_scale), need_norm=self._step_scale != 1.0)
             self.sched_step += 1
             self._check_scale()
@@ -643,6 +686,8 @@ class Trainer:
             sd["lora"] = self.adapter.train_state()
         if self.sam is not None:
             sd["sam"] = asdict(self.sam)                 # for information only: SAM keeps no state between steps, load_state_dict ignores it
+        if self.anchor is not None:                      # w0 and F stay out (two more copies of the network): whoever resumes reloads them
+            sd["anchor"] = {"lam": float(self.anchor.lam), "mode": self.anchor.mode}
         if self.keep_pruned is not None:
             sd["keep_pruned"] = self.keep_pruned.keep.detach().to("cpu", torch.float32).clone()
         return sd
@@ -654,6 +699,9 @@ class Trainer:
         if ("keep_pruned" in sd) != (self.keep_pruned is not None):
             raise ValueError("load_state_dict: the state " + ("holds a" if "keep_pruned" in sd else "holds no") + " prune mask but this trainer was "
                              "built " + ("without" if "keep_pruned" in sd else "with") + " one (Trainer keep_pruned=...)")
+        if ("anchor" in sd) != (self.anchor is not None):
+            raise ValueError("load_state_dict: the state " + ("was written with an" if "anchor" in sd else "was written without an") + " anchor "
+                             "but this trainer was built " + ("without" if "anchor" in sd else "with") + " one (Trainer anchor=...)")
         if self.keep_pruned is not None and not torch.equal(sd["keep_pruned"].to("cpu", torch.float32), self.keep_pruned.keep.to("cpu", torch.float32)):
             raise ValueError("load_state_dict: the state was written under a different prune mask than this trainer's keep_pruned")
         if self.adapter is not None:
