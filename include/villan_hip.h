@@ -614,6 +614,37 @@ int vd_channel_stats(const int64_t* host_table, const int64_t* table, int n_jobs
  * vd_neuron_scale's layout (one wave per row; an aligned row moves as f32x4, any other as scalars).  Every other float of buf -- kept rows,
  * biases, floats outside the table -- is neither read nor written.  One launch for the network. */
 int vd_neuron_keep_rows(float* buf, const int64_t* table, int n_jobs, int64_t total_blocks, const float* keep, void* stream);
+/* Channel Lipschitzness-based Pruning (clp.py) -- csrc/vd_clp.hip.
+ *
+ * vd_channel_lipschitz: out[first neuron + j] = sigma_max(W_j) * |scale[first neuron + j]| for every weight row of a network, W_j the row seen
+ * as a [Cin, T] matrix, in one launch.  A LIPSCHITZ TABLE of n_jobs x 6 int64 is given twice: `host_table` in host memory (every job is checked
+ * there before any launch) and `table`, the same bytes in device memory.  A job is
+ *   {weight offset in floats, rows, Cin, T, first neuron, first workgroup}
+ * with the weight [rows, Cin, T] contiguous at w + offset; T = 9 (3x3 convolutions) or 1 (1x1 convolutions, linears, attention projections).
+ * The neuron-table convention: one 64-lane wave per row, four rows per 256-thread workgroup, a job owns ceil(rows / 4) workgroups; first
+ * neurons ascend from 0 by rows, first workgroups from 0 by that count, and total_blocks is their sum.
+ *   Gram stage.  G = W_j^T W_j, the T (T + 1) / 2 entries (i, j), i <= j, entry e = i * 9 - i * (i - 1) / 2 + (j - i) (the upper triangle row
+ *   by row).  Lane l takes the input channels l, l + 64, ... in ascending order, one f32 partial per entry from +0, p_e = p_e + w[c][i] * w[c][j]
+ *   with the product and the sum rounded on their own; the 64 lanes are added by the fixed xor tree (offsets 32, 16, ..., 1).  No atomics:
+ *   bit-reproducible.  The longest chain of additions is ceil(Cin / 64) + 6 (vd_channel_lipschitz_plan reports it).
+ *   Eigen stage.  T = 1: lambda_max = G_00.  T = 9: G is scaled by a power of two so that its largest diagonal entry lies in [1, 2) and
+ *   diagonalised in f32 by cyclic Jacobi, 8 sweeps over the pairs (p, q), p < q, row by row, with Rutishauser's rotation formulas and
+ *   correctly rounded division and square root; a pair with |a_pq| <= 2^-30 is left alone, so a diagonal G gives exactly max_i G_ii.
+ *   lambda_max is the largest diagonal entry after the last sweep.  Relative error of lambda_max: at most 5760.5 * 2^-24 (each of the at most
+ *   288 rotations moves it by at most 20 * 2^-24 lambda_max: 4 roundings per updated entry and the rounding of c, s, tau, over rows and columns
+ *   of Frobenius norm at most 2 lambda_max; 2^-25 for the pairs left alone and the off-diagonal rest after the last sweep) -- a worst case
+ *   over the operation count; a few 2^-24 is what is measured.
+ *   out = sqrtf(lambda_max) * fabsf(scale) (scale NULL: no factor), WRITTEN, never accumulated; a zero row gives +0.0.
+ *   gram != NULL: the row's Gram entries are also written at gram[45 * neuron + e]; a T = 1 row writes slot 0 and touches no other.
+ * A row is staged through LDS in pieces of 576 floats: f32x4 loads where the job starts 16-byte aligned and Cin * T is a multiple of 4, scalar
+ * loads otherwise, with the same values and sums either way.  w is read once; nothing but out and gram is written.  out and scale hold one
+ * float per neuron of the table, gram 45.
+ * VD_EINVAL before any launch: a null w, host_table, table or out; n_jobs < 1; T outside {1, 9}; rows < 1 or Cin < 1; a negative offset; first
+ * neurons, first workgroups or a total_blocks that break the rule above.
+ * vd_channel_lipschitz_plan (host only): the chain length of a row of Cin channels and T taps. */
+int vd_channel_lipschitz_plan(int Cin, int T, int64_t* chain);
+int vd_channel_lipschitz(const float* w, const int64_t* host_table, const int64_t* table, int n_jobs, int64_t total_blocks, const float* scale,
+                         float* out, float* gram, void* stream);
 /* Anchored fine-tuning (anchor.py, Trainer(anchor=...)) -- csrc/vd_anchor.hip: the penalty lambda / 2 * sum_i F_i (w_i - w0_i)^2 that holds the
  * weights to a starting point w0 (EWC, Kirkpatrick et al. 2017, F the diagonal Fisher information; F = 1: L2-SP, Li et al. 2018).  Plain C++ with
  * vector loads and stores, no atomics, every operation rounded on its own (no FMA contraction), every sum in a fixed order: bit-reproducible.

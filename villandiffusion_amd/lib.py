@@ -130,6 +130,8 @@ PROTOTYPES = {
     "vd_channel_stats_ws_floats": (_i64, [_vp, _i32]),
     "vd_channel_stats": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
     "vd_neuron_keep_rows": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
+    "vd_channel_lipschitz_plan": (_i32, [_i32, _i32, C.POINTER(_i64)]),
+    "vd_channel_lipschitz": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     "vd_anchor_plan": (_i32, [_i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "vd_fisher_accum": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "vd_anchor_grad": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),

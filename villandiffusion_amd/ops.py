@@ -1467,6 +1467,42 @@ def neuron_keep_rows(buf, tab, keep):
     return buf
 
 
+LIPSCHITZ_JOB_INTS = 6    # weight offset, rows, Cin, T, first neuron, first workgroup
+LIPSCHITZ_GRAM = 45       # gram slots per neuron: the upper triangle of a 9 x 9 Gram matrix, row by row
+LIPSCHITZ_SWEEPS = 8
+LIPSCHITZ_EIGEN_BOUND = 5760.5 * 2.0 ** -24     # relative error of lambda_max the header of vd_channel_lipschitz derives
+
+
+def channel_lipschitz_plan(Cin: int, T: int) -> int:
+    """The longest chain of additions of a Gram entry of a [Cin, T] row of vd_channel_lipschitz: asked of the library on the host."""
+    chain = C.c_int64(0)
+    L.check(L.load().vd_channel_lipschitz_plan(int(Cin), int(T), C.byref(chain)), "vd_channel_lipschitz_plan")
+    return chain.value
+
+
+def channel_lipschitz(w, host_table, out, scale=None, gram=None, table=None):
+    """out[first neuron + j] = sigma_max of row j of every job of the Lipschitz table, the row seen as [Cin, T], times |scale[.]| where given
+    (vd_channel_lipschitz: one launch for the table, w read once, fixed order, bit-reproducible).  host_table: [n_jobs, 6] int64 on the host,
+    {weight offset, rows, Cin, T, first neuron, first workgroup}; table: the same on w's device (uploaded here when None).  gram:
+    [n_neurons, 45] f32 or None, the Gram entries of every row.  Every extent is checked here, on the host; the table's rules by the library."""
+    assert host_table.dtype == torch.int64 and host_table.dim() == 2 and host_table.shape[1] == LIPSCHITZ_JOB_INTS and host_table.is_contiguous()
+    assert host_table.device.type == "cpu" and host_table.shape[0] >= 1
+    assert w.is_contiguous() and w.dtype == torch.float32
+    jobs = host_table.tolist()
+    n = sum(j[1] for j in jobs)
+    blocks = sum((j[1] + 3) // 4 for j in jobs)
+    assert all(j[0] >= 0 and j[0] + j[1] * j[2] * j[3] <= w.numel() for j in jobs if min(j[1:4]) >= 1), "a job leaves the weight buffer"
+    for v, per in ((out, 1), (scale, 1), (gram, LIPSCHITZ_GRAM)):
+        assert v is None or (v.is_contiguous() and v.dtype == torch.float32 and v.numel() == per * n and v.device == w.device), "one entry per neuron"
+    if table is None:
+        table = upload_table(host_table, w.device)
+    nbytes = 4.0 * sum(j[1] * j[2] * j[3] for j in jobs) + 4.0 * n * (1 + (scale is not None))
+    _timed("channel_lipschitz (channel_lipschitz_kernel)", nbytes, "hbm", lambda: L.check(     # every weight read once; one float per row written
+        _lib().vd_channel_lipschitz(_p(w), host_table.data_ptr(), _p(table), len(jobs), blocks, _p(scale), _p(out), _p(gram), _s()),
+        "vd_channel_lipschitz"))
+    return out
+
+
 # --------------------------------------------------------------------------------------------- samplers / data
 def sched_step(x, eps, out, *, c_eps, c_div, clip, c_x0, c_x, c_e, c_z, z=None, x0_out=None, seed=0, offset=0):
     assert x.is_contiguous() and eps.is_contiguous() and out.is_contiguous()
