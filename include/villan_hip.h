@@ -669,6 +669,30 @@ int vd_fisher_accum(float* F, const float* g, int64_t n, float s, void* stream);
  * partial: >= 1024 floats of scratch, needed with pen only.  pen NULL: no sum is formed, neither partial nor pen is touched.  w, w0 and F are
  * read only; g, w, w0, F do not overlap each other or the scratch.  20 B/float (16 without F). */
 int vd_anchor_grad(float* g, const float* w, const float* w0, const float* F, int64_t n, float coef, float* partial, float* pen, void* stream);
+/* Mode Connectivity Repair (curve.py: Curve, CurveAdam) -- csrc/vd_curve.hip: a point of a one-bend curve between two checkpoints A and B of
+ * one architecture (Garipov et al. 2018; Zhao et al. 2020), phi = ca * A + cm * theta + cb * B over whole flat weight buffers, and the squared
+ * sides of the triangle (A, theta, B).  Plain C++ with vector loads and stores, no atomics, every operation rounded on its own (no FMA
+ * contraction), every sum in a fixed order: bit-reproducible.  Both kernels walk the n floats as vd_sam_perturb does: items of four from the
+ * buffer's start, item q in thread q % (grid * block), one 16-byte access where every pointer of the call is 16-byte aligned, four scalar ones
+ * otherwise (and for a last, partial item), with the same values and the same sums either way.  Pointers are 4-byte aligned.
+ *
+ * vd_curve_plan (host only): the launch shape of both kernels for n floats.  It is vd_sam_plan's rule:
+ *   block = 256, floats_per_thread = 16, grid = clamp(ceil(n / (block * floats_per_thread)), 1, 1024); past the cap a thread strides on. */
+int vd_curve_plan(int64_t n, int* grid, int* block, int* floats_per_thread);
+/* out[i] = (ca * wa[i] + cm * wm[i]) + cb * wb[i]: three products and two sums in that order, each rounded to f32.  The three inputs may be
+ * one another (the midpoint of the chord is wm = wa with cm = 0); out overlaps none of them.  n = 0 returns 0 without a launch.  A raw write of
+ * weights where out is a network's: the caller invalidates what it derived from them.  16 B/float.
+ * VD_EINVAL before any launch: n < 0, a NULL pointer, out overlapping an input, a non-finite coefficient. */
+int vd_curve_point(float* out, const float* wa, const float* wm, const float* wb, int64_t n, float ca, float cm, float cb, void* stream);
+/* out3 = {sum_i (wm[i] - wa[i])^2, sum_i (wm[i] - wb[i])^2, sum_i (wa[i] - wb[i])^2} (a device array), every difference and every square rounded
+ * to f32, each sum added in vd_sam_norm_sq's two stages:
+ *   1. a thread keeps one f32 partial per position k % 4 over its items in ascending order, adds them as (a0 + a1) + (a2 + a3); the 64 lanes
+ *      of a wave are added by a fixed xor tree, the four waves as (r0 + r1) + (r2 + r3); partial[s * 1024 + workgroup] holds sum s;
+ *   2. one workgroup: per sum, thread t adds partial[t], partial[t + 256], ... in that order, then the same tree.
+ * The longest chain of additions is ceil(ceil(n / 4) / (grid * block)) + ceil(grid / 256) + 18.
+ * partial: >= 3 * 1024 floats of scratch.  The three inputs are read once and may be one another; n = 0 writes three +0.0.  12 B/float.
+ * VD_EINVAL before any launch: n < 0, a NULL pointer, the scratch or out3 overlapping an input or each other. */
+int vd_curve_geometry(const float* wa, const float* wm, const float* wb, int64_t n, float* partial, float* out3, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10 -- sampler steps (diffusers *Scheduler.step, via pipeline(...) VillanDiffusion.py:579).

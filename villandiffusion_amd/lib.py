@@ -135,6 +135,9 @@ PROTOTYPES = {
     "vd_anchor_plan": (_i32, [_i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "vd_fisher_accum": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "vd_anchor_grad": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
+    "vd_curve_plan": (_i32, [_i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "vd_curve_point": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _vp]),
+    "vd_curve_geometry": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "vd_sched_step": (_i32, [_vp] * 5 + [_i64] + [_f32] * 7 + [C.c_uint64, C.c_uint64, _vp]),
     "vd_batch_l2norm": (_i32, [_vp, _vp, _i32, _i64, _vp]),
     "vd_postprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _vp]),

@@ -1403,6 +1403,35 @@ def anchor_grad(g, w, w0, F, coef: float, partial=None, pen=None):
     return g
 
 
+def curve_plan(n: int):
+    """(grid, block, floats per thread) of vd_curve_point and vd_curve_geometry for n floats: asked of the library on the host."""
+    g, b, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    L.check(L.load().vd_curve_plan(int(n), C.byref(g), C.byref(b), C.byref(f)), "vd_curve_plan")
+    return g.value, b.value, f.value
+
+
+def curve_point(out, wa, wm, wb, ca: float, cm: float, cb: float, weights=True):
+    """out = (ca * wa + cm * wm) + cb * wb, every operation rounded on its own (vd_curve_point: one pass, no temporary).  The inputs may be one
+    another; out is none of them.  weights=False: `out` is no network parameter (the bend, a scratch buffer): caches derived from the weights
+    stay valid.  Otherwise a raw-pointer write of weights: WEIGHTS_EPOCH is bumped here and the caller calls the network's weights_changed()."""
+    global WEIGHTS_EPOCH
+    n = _sam_flat(out, wa, wm, wb)
+    if weights:
+        WEIGHTS_EPOCH += 1
+    _timed("curve_point (curve_point_kernel)", 16.0 * n, "hbm", lambda: L.check(                         # wa, wm, wb read; out written
+        _lib().vd_curve_point(_p(out), _p(wa), _p(wm), _p(wb), n, float(ca), float(cm), float(cb), _s()), "vd_curve_point"))
+    return out
+
+
+def curve_geometry(wa, wm, wb, partial, out3):
+    """out3 = [sum (wm - wa)^2, sum (wm - wb)^2, sum (wa - wb)^2] in vd_sam_norm_sq's fixed order (vd_curve_geometry: one read of the three)."""
+    n = _sam_flat(wa, wm, wb)
+    assert partial.numel() >= 3 * 1024 and partial.dtype == torch.float32 and out3.numel() >= 3 and out3.dtype == torch.float32
+    _timed("curve_geometry (curve_geometry_kernel)", 12.0 * n, "hbm", lambda: L.check(
+        _lib().vd_curve_geometry(_p(wa), _p(wm), _p(wb), n, _p(partial), _p(out3), _s()), "vd_curve_geometry"))
+    return out3
+
+
 CHANNEL_ACTS = {"raw": 0, "silu_gn": 1}
 CHANNEL_JOB_INTS = 11     # x, mean, rstd, gamma, beta, B, C, HW, G, first channel, first workgroup
 
