@@ -693,6 +693,49 @@ int vd_curve_point(float* out, const float* wa, const float* wm, const float* wb
  * partial: >= 3 * 1024 floats of scratch.  The three inputs are read once and may be one another; n = 0 writes three +0.0.  12 B/float.
  * VD_EINVAL before any launch: n < 0, a NULL pointer, the scratch or out3 overlapping an input or each other. */
 int vd_curve_geometry(const float* wa, const float* wm, const float* wb, int64_t n, float* partial, float* out3, void* stream);
+/* Checkpoint merging (merge.py: merge, merge_scan) -- csrc/vd_merge.hip: task arithmetic (Ilharco et al. 2023) and TIES-Merging (Yadav et al.
+ * 2023) of up to 8 checkpoints of one layout over whole flat weight buffers, tau_i = theta_i - theta_base the task vectors.  Plain C++ with
+ * vector loads and stores, every operation rounded to f32 on its own (no FMA contraction), no float atomics and no global atomics (LDS integer
+ * adds into histogram bins only: integer counts do not depend on order): bit-reproducible.  The kernels walk the n floats as vd_curve_point
+ * does: items of four from the buffer's start, item q in thread q % (grid * block), one 16-byte access where every data pointer of the call is
+ * 16-byte aligned, four scalar ones otherwise (and for a last, partial item), with the same bits either way.  n >= 2^31 is VD_EINVAL
+ * everywhere (the per-workgroup counts are 32-bit).
+ * Two deliberate departures from the published TIES code: the k largest magnitudes are kept with ties at the threshold ALL kept (the published
+ * code keeps k + 1), and a sign sum of exactly zero elects + (the published code takes the majority sign of the whole vector there).
+ *
+ * vd_merge_plan (host only): the launch shape of the kernels below for n floats, vd_curve_plan's rule
+ *   block = 256, floats_per_thread = 16, grid = clamp(ceil(n / (block * floats_per_thread)), 1, 1024); past the cap a thread strides on,
+ * and ws_bytes = 32 + grid * 257 * 4, the scratch vd_merge_select needs for n floats. */
+enum { VD_MERGE_LINEAR = 0, VD_MERGE_TIES = 1 };
+int vd_merge_plan(int64_t n, int* grid, int* block, int* floats_per_thread, int64_t* ws_bytes);
+/* Exact selection: with d[j] = w[j] - base[j] (one f32 subtraction) and key[j] the bits of |d[j]| as uint32 (non-negative floats order like
+ * their bits), thr_out[0] (a device f32) = the k-th largest key, 0 <= k <= n, found by radix selection in FOUR PASSES OF 8 BITS, most
+ * significant byte first.  Each pass reads w and base once, counts the keys that match the prefix found so far into per-workgroup LDS bins
+ * and writes them to ws; a one-workgroup finish adds them in 64 bits, walks the bins from the top and moves the prefix and the remaining rank
+ * (kept in ws) on.  A fixed launch sequence on `stream`, no read-back between passes.  8 B/float per pass.
+ *   rec[0] = n_gt, keys above the threshold; rec[1] = n_eq, keys equal to it; rec[2] = n_nonfinite, keys >= 0x7F800000 (inf and NaN; counted
+ *   in the first pass whatever k is).  INVARIANT for 1 <= k <= n:  n_gt < k <= n_gt + n_eq.
+ *   k = 0: thr_out = +inf, n_gt = n_eq = 0 (one pass, for n_nonfinite).  k = n: the minimum.  n = 0: nothing that reads w is launched; +inf
+ *   and three zeros are written.
+ * w and base are read only and may be one another.  ws: >= ws_bytes of vd_merge_plan(n), 8-byte aligned; rec: 3 int64.
+ * VD_EINVAL before any launch: a NULL or misaligned pointer, k outside [0, n], ws, thr_out or rec overlapping an input or each other. */
+int vd_merge_select(const float* w, const float* base, int64_t n, int64_t k, void* ws, float* thr_out, int64_t* rec, void* stream);
+/* The merge, one pass with no temporary.  tasks: a HOST array of K device pointers, 1 <= K <= 8; lam: a HOST array of K floats (both read at
+ * the call; lam is ignored and may be NULL with VD_MERGE_TIES); thr: a DEVICE array of K floats, what vd_merge_select wrote, or zeros for
+ * "keep everything".  Per element j, with d_i = tasks[i][j] - base[j] and t_i = (|d_i| >= thr[i]) ? d_i : +0.0f:
+ *   VD_MERGE_LINEAR:  acc = 0; for i ascending: acc = acc + lam[i] * t_i;  out[j] = base[j] + acc.
+ *   VD_MERGE_TIES:    s = 0; for i ascending: s = s + t_i;  the elected sign is + where s >= 0, else -;
+ *                     m = 0, c = 0; for i ascending, if t_i != 0 and its sign is the elected one: m = m + t_i, c += 1;
+ *                     tau = c ? m / (float)c : +0.0f (an IEEE division);  out[j] = base[j] + lam_out * tau.
+ * stats (2 K + 2 device int64): kept[i] = #(|d_i| >= thr[i]) (= n_gt + n_eq of the matching select); won[i] = the entries of task i that
+ * entered m (LINEAR: its non-zero kept entries); support = positions with any non-zero t_i; conflict = positions with non-zero t_i of both
+ * signs.  Per-workgroup uint32 counts go to partial (>= (2 K + 2) * 1024 uint32), a one-workgroup finish adds them in 64 bits.
+ * out may be exactly base or exactly one tasks[i] (in place: a thread reads an element before it writes it), otherwise it overlaps none of
+ * them; the inputs may be one another.  n = 0: no launch over the data, stats all zero.  4 (K + 2) B/float.
+ * VD_EINVAL before any launch: K outside [1, 8], an unknown mode, a NULL or misaligned pointer or entry of tasks, out overlapping an input
+ * partially, a non-finite lam[i] (LINEAR) or lam_out, partial or stats overlapping anything else. */
+int vd_merge_apply(float* out, const float* base, const float* const* tasks, const float* lam, const float* thr, int K, int64_t n, int mode,
+                   float lam_out, uint32_t* partial, int64_t* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10 -- sampler steps (diffusers *Scheduler.step, via pipeline(...) VillanDiffusion.py:579).

@@ -1432,6 +1432,54 @@ def curve_geometry(wa, wm, wb, partial, out3):
     return out3
 
 
+MERGE_MODES = {"linear": 0, "ties": 1}
+MERGE_MAX_TASKS = 8
+MERGE_SELECT_PASSES = 4          # vd_merge_select: four passes of 8 bits
+MERGE_PARTIAL = 18 * 1024        # uint32 of vd_merge_apply's scratch: (2 K + 2) * 1024 at K = 8
+
+
+def merge_plan(n: int):
+    """(grid, block, floats per thread, scratch bytes of merge_select) of vd_merge_select and vd_merge_apply for n floats: asked of the library
+    on the host."""
+    g, b, f, w = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    L.check(L.load().vd_merge_plan(int(n), C.byref(g), C.byref(b), C.byref(f), C.byref(w)), "vd_merge_plan")
+    return g.value, b.value, f.value, w.value
+
+
+def merge_select(w, base, k: int, ws, thr_out, rec):
+    """thr_out[0] = the k-th largest |w - base| exactly (k = 0: +inf), rec = [keys above it, keys equal to it, non-finite keys] (vd_merge_select:
+    radix selection over the float bits, four passes of 8 bits, no read-back).  ws: >= merge_plan(n)[3] bytes (uint8), rec: 3 int64."""
+    n = _sam_flat(w, base)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= merge_plan(n)[3], "ws: merge_plan(n)[3] bytes of uint8"
+    assert thr_out.dtype == torch.float32 and thr_out.numel() >= 1 and rec.dtype == torch.int64 and rec.numel() >= 3 and rec.is_contiguous()
+    passes = MERGE_SELECT_PASSES if k else 1
+    _timed("merge_select (merge_hist_kernel)", 8.0 * n * passes, "hbm", lambda: L.check(                 # w, base read once per pass
+        _lib().vd_merge_select(_p(w), _p(base), n, int(k), _p(ws), _p(thr_out), _p(rec), _s()), "vd_merge_select"))
+    return thr_out
+
+
+def merge_apply(out, base, tasks: Sequence[torch.Tensor], lam: Optional[Sequence[float]], thr, mode: str, lam_out: float, partial, stats,
+                weights=True):
+    """The merge of K task checkpoints into `out` in one pass (vd_merge_apply): with t_i = tasks[i] - base trimmed at thr[i], "linear" is
+    out = base + sum_i lam[i] t_i (added in ascending i), "ties" out = base + lam_out * (the mean of the t_i that carry the elected sign).
+    out may be `base` or one of the tasks.  stats (2 K + 2 int64): kept[K], won[K], support, conflict.  weights=False: `out` is no network
+    parameter.  Otherwise a raw-pointer write of weights: WEIGHTS_EPOCH is bumped here and the caller calls the network's weights_changed()."""
+    global WEIGHTS_EPOCH
+    K = len(tasks)
+    n = _sam_flat(out, base, *tasks)
+    assert thr.dtype == torch.float32 and thr.numel() >= K and thr.is_contiguous()
+    assert partial.dtype == torch.int32 and partial.numel() >= (2 * K + 2) * 1024 and stats.dtype == torch.int64 and stats.numel() >= 2 * K + 2
+    ptrs = (C.c_void_p * max(K, 1))(*[t.data_ptr() for t in tasks])
+    lams = None if lam is None else (C.c_float * max(K, 1))(*[float(v) for v in lam])
+    assert lam is None or len(lam) == K, f"merge_apply: {len(lam)} coefficients for {K} tasks"
+    if weights:
+        WEIGHTS_EPOCH += 1
+    _timed("merge_apply (merge_apply_kernel)", 4.0 * (K + 2) * n, "hbm", lambda: L.check(                # base and K tasks read; out written
+        _lib().vd_merge_apply(_p(out), _p(base), ptrs, lams, _p(thr), K, n, MERGE_MODES[mode], float(lam_out), _p(partial), _p(stats), _s()),
+        "vd_merge_apply"))
+    return out
+
+
 CHANNEL_ACTS = {"raw": 0, "silu_gn": 1}
 CHANNEL_JOB_INTS = 11     # x, mean, rstd, gamma, beta, B, C, HW, G, first channel, first workgroup
 
