@@ -736,6 +736,34 @@ int vd_merge_select(const float* w, const float* base, int64_t n, int64_t k, voi
  * partially, a non-finite lam[i] (LINEAR) or lam_out, partial or stats overlapping anything else. */
 int vd_merge_apply(float* out, const float* base, const float* const* tasks, const float* lam, const float* thr, int K, int64_t n, int mode,
                    float lam_out, uint32_t* partial, int64_t* stats, void* stream);
+/* vd_merge_apply with a seeded random drop of every task vector: DARE (Yu et al., ICML 2024: drop with probability p, rescale the survivors
+ * by 1 / (1 - p); VD_MERGE_LINEAR is DARE-linear, VD_MERGE_TIES DARE-TIES) and, with VD_DROP_COPY, Fine-mixing (Zhang et al., Findings of
+ * EMNLP 2022).  tasks, lam, drop_thr, rescale and streams are HOST arrays of K entries read at the call; thr is the DEVICE array of
+ * vd_merge_apply.  The walk, the alignment rule, n < 2^31 and n = 0 are vd_merge_apply's, the launch shape vd_merge_plan's.
+ * The draw is a pure function of (seed, streams[i], element index j counted from the buffer's start -- never of an address):
+ *   q = j >> 2;  r = philox4x32_10(counter = (lo32(q), hi32(q), streams[i], 1), key = (lo32(seed), hi32(seed)))[j & 3];
+ *   keep_i = (uint64)r >= drop_thr[i],   0 <= drop_thr[i] <= 2^32:  0 keeps everything, 2^32 nothing; an integer Bernoulli whose keep
+ *   probability is exactly (2^32 - drop_thr[i]) / 2^32.
+ * Counter word 3 is 1; vd_randn and vd_sched_step use 0 there, so no noise draw of the same seed shares a counter.  One Philox call serves
+ * the four floats of an item for one task.
+ * Per element j, with d_i = tasks[i][j] - base[j]:
+ *   t_i = (|d_i| >= thr[i] && keep_i) ? (VD_DROP_RESCALE ? d_i * rescale[i] : d_i) : +0.0f,
+ * then VD_MERGE_LINEAR / VD_MERGE_TIES proceed word for word as stated for vd_merge_apply, every operation rounded to f32 on its own.  With
+ * every drop_thr[i] = 0 and no VD_DROP_RESCALE the bits and the counts are vd_merge_apply's; with drop_thr[i] = 2^32 out is base (a -0.0 of
+ * base becomes +0.0 as at lam = 0) and drawn = 0.  rescale is the caller's number (DARE: f32(1 / (1 - p)) of the nominal p).
+ * VD_DROP_COPY (K = 1 and VD_MERGE_LINEAR; thr, lam, rescale and lam_out are ignored and may be NULL):  out[j] = keep_0 ? tasks[0][j] :
+ *   base[j], the bits copied, -0.0, denormals and NaN payloads included.  12 B/float.
+ * stats (3 K + 2 device int64): drawn[i] = #keep_i (a function of seed, streams[i], drop_thr[i] and n only); kept[i] = #(|d_i| >= thr[i] &&
+ * keep_i); won[i], support and conflict as in vd_merge_apply.  VD_DROP_COPY: kept[0] = won[0] = drawn[0], support = #(keep_0 and tasks[0][j]
+ * != base[j] as floats), conflict = 0.  Per-workgroup uint32 counts go to partial (>= (3 K + 2) * 1024 uint32), a one-workgroup finish adds
+ * them in 64 bits.  No float atomics and no global atomics.
+ * out may be exactly base or exactly one tasks[i], otherwise it overlaps none of them; the inputs may be one another.  4 (K + 2) B/float.
+ * VD_EINVAL before any launch: everything vd_merge_apply refuses, a NULL drop_thr or streams, drop_thr[i] > 2^32, VD_DROP_RESCALE with a NULL
+ * or non-finite rescale[i], unknown flag bits, VD_DROP_COPY with VD_DROP_RESCALE, with K != 1 or with a mode other than VD_MERGE_LINEAR. */
+enum { VD_DROP_RESCALE = 1, VD_DROP_COPY = 2 };
+int vd_merge_apply_drop(float* out, const float* base, const float* const* tasks, const float* lam, const float* thr, const uint64_t* drop_thr,
+                        const float* rescale, const uint32_t* streams, int K, int64_t n, int mode, float lam_out, uint64_t seed, int flags,
+                        uint32_t* partial, int64_t* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10 -- sampler steps (diffusers *Scheduler.step, via pipeline(...) VillanDiffusion.py:579).

@@ -5,7 +5,9 @@
 //                    a fixed launch sequence with no read-back in between.  It also gives n_gt (keys above the threshold), n_eq (keys equal
 //                    to it) and the count of inf / NaN keys; INVARIANT for 1 <= k <= n:  n_gt < k <= n_gt + n_eq;
 //   vd_merge_apply   trims every task vector at its threshold and forms the merged weights in ONE pass with no temporary, with the integer
-//                    counts the read-outs come from (kept, won, support, conflict).
+//                    counts the read-outs come from (kept, won, support, conflict);
+//   vd_merge_apply_drop  the same pass with a seeded random drop of every task vector (DARE, Yu et al. 2024) or, with VD_DROP_COPY, the
+//                    mix of a fine-tune with its base (Fine-mixing, Zhang et al. 2022): Philox4x32-10 on (seed, stream, element index).
 // HBM-bound, plain C++ with vector loads and stores.  No float atomics and no global atomics: the only atomics are LDS integer adds into
 // histogram bins, and integer counts do not depend on order, so a repeat is bit-identical.  Compiled without FMA contraction: every difference,
 // product, sum and the division is rounded to f32 on its own, so the elementwise part is the numpy float32 op sequence bit for bit.
@@ -323,6 +325,218 @@ __global__ __launch_bounds__(256) void merge_apply_finish_kernel(const uint32_t*
     }
 }
 
+// ---- the seeded drop (DARE, Fine-mixing): vd_merge_apply_drop -------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., Random123), restated from vd_elem.hip so that nothing of the training path is built differently; both are
+// pinned to tests/elem_ref.py's integer restatement.
+__device__ __forceinline__ void mrg_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                                  uint32_t (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+constexpr uint64_t MRG_DROP_ALL = (uint64_t)1 << 32;      // drop_thr: 0 keeps every entry, 2^32 none
+
+// The keep bits of item q for one task: bit e = ((uint64)r[e] >= T), r the Philox words of counter (lo32(q), hi32(q), stream, 1).  T = 0 and
+// T = 2^32 need no draw (the branch is uniform: T is a kernel argument).
+__device__ __forceinline__ uint32_t drop_keep_bits(int64_t q, uint32_t stream_id, uint64_t T, uint32_t k0, uint32_t k1) {
+    if (T == 0) return 15u;
+    if (T >= MRG_DROP_ALL) return 0u;
+    uint32_t r[4];
+    mrg_philox4x32_10((uint32_t)(uint64_t)q, (uint32_t)((uint64_t)q >> 32), stream_id, 1u, k0, k1, r);
+    const uint32_t t = (uint32_t)T;
+    return (r[0] >= t ? 1u : 0u) | (r[1] >= t ? 2u : 0u) | (r[2] >= t ? 4u : 0u) | (r[3] >= t ? 8u : 0u);
+}
+
+struct DropArgs {
+    const float* task[MRG_MAXK];
+    uint64_t drop_thr[MRG_MAXK];
+    float lam[MRG_MAXK];
+    float rescale[MRG_MAXK];      // 1.0f without VD_DROP_RESCALE: d * 1.0f is d, bit for bit
+    uint32_t stream[MRG_MAXK];
+};
+
+// counters of a thread: drawn[0..K), kept[0..K), won[0..K), support, conflict
+template <int K>
+struct DropCounts {
+    uint32_t drawn[K], kept[K], won[K], support, conflict;
+};
+
+// merge_one with the keep bit of every task (bit i of `kb`) and the rescale: t_i = (|d_i| >= thr_i && keep_i) ? d_i * rescale_i : +0.0f, the
+// rest word for word.
+template <int MODE, int K>
+__device__ __forceinline__ float merge_one_drop(float b, const float (&tv)[K], uint32_t kb, const float (&thr)[K], const float (&lam)[K],
+                                                const float (&rs)[K], float lam_out, DropCounts<K>& c) {
+    float t[K];
+    bool pos_any = false, neg_any = false, any = false;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const float d = tv[i] - b;
+        const bool keep = fabsf(d) >= thr[i] && ((kb >> i) & 1u);
+        t[i] = keep ? d * rs[i] : 0.0f;
+        c.kept[i] += keep ? 1u : 0u;
+        any |= t[i] != 0.0f;
+        pos_any |= t[i] > 0.0f;
+        neg_any |= t[i] < 0.0f;
+    }
+    c.support += any ? 1u : 0u;
+    c.conflict += (pos_any && neg_any) ? 1u : 0u;
+    if (MODE == VD_MERGE_LINEAR) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            acc = acc + lam[i] * t[i];
+            c.won[i] += t[i] != 0.0f ? 1u : 0u;
+        }
+        return b + acc;
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < K; ++i) s = s + t[i];
+    const bool plus = s >= 0.0f;
+    float m = 0.0f;
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const bool in = t[i] != 0.0f && ((t[i] > 0.0f) == plus);
+        if (in) {
+            m = m + t[i];
+            ++cnt;
+        }
+        c.won[i] += in ? 1u : 0u;
+    }
+    const float tau = cnt ? __fdiv_rn(m, (float)cnt) : 0.0f;
+    return b + lam_out * tau;
+}
+
+// merge_apply_kernel's walk, with one Philox call per task and item.  partial[c * 1024 + workgroup] holds counter c of the workgroup.
+template <bool VEC, int MODE, int K>
+__global__ __launch_bounds__(256) void merge_apply_drop_kernel(float* out, const float* base, DropArgs a, const float* __restrict__ thr_dev,
+                                                               int64_t n, float lam_out, uint32_t key0, uint32_t key1,
+                                                               uint32_t* __restrict__ partial) {
+    __shared__ uint32_t red[4];
+    DropCounts<K> c;
+    float thr[K], lam[K], rs[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        c.drawn[i] = c.kept[i] = c.won[i] = 0u;
+        thr[i] = thr_dev[i];
+        lam[i] = a.lam[i];
+        rs[i] = a.rescale[i];
+    }
+    c.support = c.conflict = 0u;
+    ITEM_STRIDE(q, (n + 3) >> 2) {
+        const int64_t k0 = q << 2;
+        const int cnt = (int)(n - k0 < 4 ? n - k0 : 4);
+        uint32_t kb[4] = {0u, 0u, 0u, 0u};      // per element: bit i = task i keeps it
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const uint32_t m = drop_keep_bits(q, a.stream[i], a.drop_thr[i], key0, key1) & ((1u << cnt) - 1u);
+            c.drawn[i] += (uint32_t)__popc(m);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) kb[e] |= ((m >> e) & 1u) << i;
+        }
+        if (VEC && cnt == 4) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(base + k0);
+            f32x4 tk[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) tk[i] = *reinterpret_cast<const f32x4*>(a.task[i] + k0);
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float tv[K];
+#pragma unroll
+                for (int i = 0; i < K; ++i) tv[i] = tk[i][e];
+                o[e] = merge_one_drop<MODE, K>(b[e], tv, kb[e], thr, lam, rs, lam_out, c);
+            }
+            *reinterpret_cast<f32x4*>(out + k0) = o;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (e >= cnt) break;
+                const float b = base[k0 + e];
+                float tv[K];
+#pragma unroll
+                for (int i = 0; i < K; ++i) tv[i] = a.task[i][k0 + e];
+                out[k0 + e] = merge_one_drop<MODE, K>(b, tv, kb[e], thr, lam, rs, lam_out, c);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const uint32_t v = block_sum_u32(c.drawn[i], red);
+        if (threadIdx.x == 0) partial[i * MRG_MAXGRID + blockIdx.x] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const uint32_t v = block_sum_u32(c.kept[i], red);
+        if (threadIdx.x == 0) partial[(K + i) * MRG_MAXGRID + blockIdx.x] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const uint32_t v = block_sum_u32(c.won[i], red);
+        if (threadIdx.x == 0) partial[(2 * K + i) * MRG_MAXGRID + blockIdx.x] = v;
+    }
+    const uint32_t sup = block_sum_u32(c.support, red);
+    const uint32_t con = block_sum_u32(c.conflict, red);
+    if (threadIdx.x == 0) {
+        partial[(3 * K) * MRG_MAXGRID + blockIdx.x] = sup;
+        partial[(3 * K + 1) * MRG_MAXGRID + blockIdx.x] = con;
+    }
+}
+
+// VD_DROP_COPY (Fine-mixing): out[j] = keep ? task[j] : base[j], the bits moved as integers.  Counters: drawn, kept = drawn, won = drawn,
+// support = #(keep and task[j] != base[j] as floats), conflict = 0.
+template <bool VEC>
+__global__ __launch_bounds__(256) void merge_mix_kernel(float* out, const float* base, const float* task, int64_t n, uint32_t stream_id,
+                                                        uint64_t T, uint32_t key0, uint32_t key1, uint32_t* __restrict__ partial) {
+    __shared__ uint32_t red[4];
+    uint32_t drawn = 0u, differ = 0u;
+    ITEM_STRIDE(q, (n + 3) >> 2) {
+        const int64_t k0 = q << 2;
+        const int cnt = (int)(n - k0 < 4 ? n - k0 : 4);
+        const uint32_t m = drop_keep_bits(q, stream_id, T, key0, key1) & ((1u << cnt) - 1u);
+        drawn += (uint32_t)__popc(m);
+        if (VEC && cnt == 4) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(base + k0);
+            const f32x4 w = *reinterpret_cast<const f32x4*>(task + k0);
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool keep = (m >> e) & 1u;
+                differ += (keep && w[e] != b[e]) ? 1u : 0u;
+                o[e] = __uint_as_float(keep ? __float_as_uint(w[e]) : __float_as_uint(b[e]));
+            }
+            *reinterpret_cast<f32x4*>(out + k0) = o;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (e >= cnt) break;
+                const float b = base[k0 + e], w = task[k0 + e];
+                const bool keep = (m >> e) & 1u;
+                differ += (keep && w != b) ? 1u : 0u;
+                out[k0 + e] = __uint_as_float(keep ? __float_as_uint(w) : __float_as_uint(b));
+            }
+        }
+    }
+    const uint32_t dr = block_sum_u32(drawn, red);
+    const uint32_t df = block_sum_u32(differ, red);
+    if (threadIdx.x == 0) {
+        partial[0 * MRG_MAXGRID + blockIdx.x] = dr;
+        partial[1 * MRG_MAXGRID + blockIdx.x] = dr;
+        partial[2 * MRG_MAXGRID + blockIdx.x] = dr;
+        partial[3 * MRG_MAXGRID + blockIdx.x] = df;
+        partial[4 * MRG_MAXGRID + blockIdx.x] = 0u;
+    }
+}
+
 inline bool finite_f(float v) { return v > -INFINITY && v < INFINITY; }      // NaN fails
 inline bool disjoint_b(const void* a, int64_t na, const void* b, int64_t nb) {      // [a, a + na bytes) and [b, b + nb bytes)
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -335,6 +549,20 @@ void launch_apply(int K, int grid, hipStream_t st, float* out, const float* base
 #define MRG_CASE(KK)                                                                                                                  \
     case KK:                                                                                                                          \
         hipLaunchKernelGGL((merge_apply_kernel<VEC, MODE, KK>), dim3(grid), dim3(MRG_BLOCK), 0, st, out, base, a, thr, n, lam_out, partial); \
+        break;
+    switch (K) {
+        MRG_CASE(1) MRG_CASE(2) MRG_CASE(3) MRG_CASE(4) MRG_CASE(5) MRG_CASE(6) MRG_CASE(7) MRG_CASE(8)
+    }
+#undef MRG_CASE
+}
+
+template <bool VEC, int MODE>
+void launch_apply_drop(int K, int grid, hipStream_t st, float* out, const float* base, const DropArgs& a, const float* thr, int64_t n,
+                       float lam_out, uint32_t key0, uint32_t key1, uint32_t* partial) {
+#define MRG_CASE(KK)                                                                                                                       \
+    case KK:                                                                                                                               \
+        hipLaunchKernelGGL((merge_apply_drop_kernel<VEC, MODE, KK>), dim3(grid), dim3(MRG_BLOCK), 0, st, out, base, a, thr, n, lam_out, key0, \
+                           key1, partial);                                                                                                 \
         break;
     switch (K) {
         MRG_CASE(1) MRG_CASE(2) MRG_CASE(3) MRG_CASE(4) MRG_CASE(5) MRG_CASE(6) MRG_CASE(7) MRG_CASE(8)
@@ -441,5 +669,74 @@ extern "C" int vd_merge_apply(float* out, const float* base, const float* const*
     }
     hipLaunchKernelGGL(merge_apply_finish_kernel, dim3(1), dim3(MRG_BLOCK), 0, ST, partial, grid, 2 * K + 2, stats);      // (n = 0: all zero)
     VD_LAUNCH_CHECK("vd_merge_apply");
+    return 0;
+}
+
+extern "C" int vd_merge_apply_drop(float* out, const float* base, const float* const* tasks, const float* lam, const float* thr,
+                                   const uint64_t* drop_thr, const float* rescale, const uint32_t* streams, int K, int64_t n, int mode,
+                                   float lam_out, uint64_t seed, int flags, uint32_t* partial, int64_t* stats, void* stream) {
+    MRG_N_OK("vd_merge_apply_drop");
+    VD_REQUIRE(K >= 1 && K <= MRG_MAXK, "vd_merge_apply_drop: K = %d lies outside [1, %d]", K, MRG_MAXK);
+    VD_REQUIRE(mode == VD_MERGE_LINEAR || mode == VD_MERGE_TIES, "vd_merge_apply_drop: unknown mode %d", mode);
+    VD_REQUIRE((flags & ~(VD_DROP_RESCALE | VD_DROP_COPY)) == 0, "vd_merge_apply_drop: unknown flag bits in %d", flags);
+    const bool copy = (flags & VD_DROP_COPY) != 0, resc = (flags & VD_DROP_RESCALE) != 0;
+    VD_REQUIRE(!(copy && resc), "vd_merge_apply_drop: VD_DROP_COPY moves bits and takes no VD_DROP_RESCALE");
+    VD_REQUIRE(!copy || (K == 1 && mode == VD_MERGE_LINEAR), "vd_merge_apply_drop: VD_DROP_COPY takes K = 1 and VD_MERGE_LINEAR, got K = %d, mode %d",
+               K, mode);
+    VD_REQUIRE(out && base && tasks && partial && stats && (copy || thr), "vd_merge_apply_drop: null pointer");
+    VD_REQUIRE(drop_thr && streams, "vd_merge_apply_drop: drop_thr or streams is null");
+    VD_REQUIRE(!resc || rescale, "vd_merge_apply_drop: VD_DROP_RESCALE needs rescale");
+    VD_REQUIRE(copy || mode == VD_MERGE_TIES || lam, "vd_merge_apply_drop: VD_MERGE_LINEAR needs lam");
+    VD_REQUIRE(copy || finite_f(lam_out), "vd_merge_apply_drop: lam_out must be finite, got %g", (double)lam_out);
+    VD_REQUIRE(((((uintptr_t)out) | ((uintptr_t)base) | ((uintptr_t)partial)) & 3) == 0 && (copy || (((uintptr_t)thr) & 3) == 0) &&
+                   (((uintptr_t)stats) & 7) == 0,
+               "vd_merge_apply_drop: out, base, thr and partial must be 4-byte aligned, stats 8-byte aligned");
+    DropArgs a;
+    const int nc = 3 * K + 2;
+    const int64_t nb = n * 4, pb = (int64_t)nc * MRG_MAXGRID * 4, sb = (int64_t)nc * 8;
+    bool vec = aligned16(out) && aligned16(base);
+    for (int i = 0; i < MRG_MAXK; ++i) {
+        a.task[i] = i < K ? tasks[i] : nullptr;
+        a.lam[i] = (i < K && !copy && mode == VD_MERGE_LINEAR) ? lam[i] : 0.0f;
+        a.rescale[i] = (i < K && resc) ? rescale[i] : 1.0f;
+        a.drop_thr[i] = i < K ? drop_thr[i] : 0;
+        a.stream[i] = i < K ? streams[i] : 0u;
+        if (i >= K) continue;
+        VD_REQUIRE(a.task[i], "vd_merge_apply_drop: tasks[%d] is null", i);
+        VD_REQUIRE((((uintptr_t)a.task[i]) & 3) == 0, "vd_merge_apply_drop: tasks[%d] is not 4-byte aligned", i);
+        VD_REQUIRE(finite_f(a.lam[i]), "vd_merge_apply_drop: lam[%d] must be finite, got %g", i, (double)a.lam[i]);
+        VD_REQUIRE(a.drop_thr[i] <= MRG_DROP_ALL, "vd_merge_apply_drop: drop_thr[%d] = %llu lies above 2^32", i, (unsigned long long)a.drop_thr[i]);
+        VD_REQUIRE(finite_f(a.rescale[i]), "vd_merge_apply_drop: rescale[%d] must be finite, got %g", i, (double)a.rescale[i]);
+        VD_REQUIRE((const void*)out == (const void*)a.task[i] || disjoint_b(out, nb, a.task[i], nb),
+                   "vd_merge_apply_drop: out overlaps tasks[%d] without being it", i);
+        VD_REQUIRE(disjoint_b(a.task[i], nb, partial, pb) && disjoint_b(a.task[i], nb, stats, sb),
+                   "vd_merge_apply_drop: tasks[%d] overlaps partial or stats", i);
+        vec = vec && aligned16(a.task[i]);
+    }
+    VD_REQUIRE((const void*)out == (const void*)base || disjoint_b(out, nb, base, nb), "vd_merge_apply_drop: out overlaps base without being it");
+    VD_REQUIRE(disjoint_b(out, nb, partial, pb) && disjoint_b(out, nb, stats, sb) && (copy || disjoint_b(out, nb, thr, K * 4)),
+               "vd_merge_apply_drop: out overlaps thr, partial or stats");
+    VD_REQUIRE(disjoint_b(base, nb, partial, pb) && disjoint_b(base, nb, stats, sb) && disjoint_b(partial, pb, stats, sb) &&
+                   (copy || (disjoint_b(thr, K * 4, partial, pb) && disjoint_b(thr, K * 4, stats, sb))),
+               "vd_merge_apply_drop: partial or stats overlaps an input or each other");
+    const uint32_t key0 = (uint32_t)seed, key1 = (uint32_t)(seed >> 32);
+    int grid = 0;
+    if (n > 0) {
+        grid = mrg_grid(n);
+        if (copy) {
+            if (vec) hipLaunchKernelGGL((merge_mix_kernel<true>), dim3(grid), dim3(MRG_BLOCK), 0, ST, out, base, a.task[0], n, a.stream[0],
+                                        a.drop_thr[0], key0, key1, partial);
+            else hipLaunchKernelGGL((merge_mix_kernel<false>), dim3(grid), dim3(MRG_BLOCK), 0, ST, out, base, a.task[0], n, a.stream[0],
+                                    a.drop_thr[0], key0, key1, partial);
+        } else if (mode == VD_MERGE_LINEAR) {
+            if (vec) launch_apply_drop<true, VD_MERGE_LINEAR>(K, grid, ST, out, base, a, thr, n, lam_out, key0, key1, partial);
+            else launch_apply_drop<false, VD_MERGE_LINEAR>(K, grid, ST, out, base, a, thr, n, lam_out, key0, key1, partial);
+        } else {
+            if (vec) launch_apply_drop<true, VD_MERGE_TIES>(K, grid, ST, out, base, a, thr, n, lam_out, key0, key1, partial);
+            else launch_apply_drop<false, VD_MERGE_TIES>(K, grid, ST, out, base, a, thr, n, lam_out, key0, key1, partial);
+        }
+    }
+    hipLaunchKernelGGL(merge_apply_finish_kernel, dim3(1), dim3(MRG_BLOCK), 0, ST, partial, grid, nc, stats);      // (n = 0: all zero)
+    VD_LAUNCH_CHECK("vd_merge_apply_drop");
     return 0;
 }

@@ -141,6 +141,8 @@ PROTOTYPES = {
     "vd_merge_plan": (_i32, [_i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
     "vd_merge_select": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "vd_merge_apply": (_i32, [_vp, _vp, C.POINTER(_vp), C.POINTER(_f32), _vp, _i32, _i64, _i32, _f32, _vp, _vp, _vp]),
+    "vd_merge_apply_drop": (_i32, [_vp, _vp, C.POINTER(_vp), C.POINTER(_f32), _vp, C.POINTER(C.c_uint64), C.POINTER(_f32), C.POINTER(C.c_uint32),
+                                   _i32, _i64, _i32, _f32, C.c_uint64, _i32, _vp, _vp, _vp]),
     "vd_sched_step": (_i32, [_vp] * 5 + [_i64] + [_f32] * 7 + [C.c_uint64, C.c_uint64, _vp]),
     "vd_batch_l2norm": (_i32, [_vp, _vp, _i32, _i64, _vp]),
     "vd_postprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _vp]),

@@ -1480,6 +1480,40 @@ def merge_apply(out, base, tasks: Sequence[torch.Tensor], lam: Optional[Sequence
     return out
 
 
+MERGE_DROP_FLAGS = {"rescale": 1, "copy": 2}
+MERGE_DROP_PARTIAL = 26 * 1024   # uint32 of vd_merge_apply_drop's scratch: (3 K + 2) * 1024 at K = 8
+
+
+def merge_apply_drop(out, base, tasks: Sequence[torch.Tensor], lam: Optional[Sequence[float]], thr, mode: str, lam_out: float,
+                     drop_thr: Sequence[int], rescale: Optional[Sequence[float]], streams: Sequence[int], seed: int, partial, stats, copy=False,
+                     weights=True):
+    """merge_apply with a seeded drop of every task vector (vd_merge_apply_drop): element j of task i is kept where word j & 3 of
+    philox4x32_10((lo32(j >> 2), hi32(j >> 2), streams[i], 1), (lo32(seed), hi32(seed))) is >= drop_thr[i] (0 .. 2^32), and the kept entries
+    are multiplied by rescale[i] (None: not at all).  copy=True (K = 1, "linear"; lam, thr, rescale and lam_out are not read): out = where(keep,
+    tasks[0], base), bits copied.  stats (3 K + 2 int64): drawn[K], kept[K], won[K], support, conflict.  `weights` as in merge_apply."""
+    global WEIGHTS_EPOCH
+    K = len(tasks)
+    n = _sam_flat(out, base, *tasks)
+    assert copy or (thr is not None and thr.dtype == torch.float32 and thr.numel() >= K and thr.is_contiguous())
+    assert partial.dtype == torch.int32 and partial.numel() >= (3 * K + 2) * 1024 and stats.dtype == torch.int64 and stats.numel() >= 3 * K + 2
+    assert len(drop_thr) == K and len(streams) == K, f"merge_apply_drop: {len(drop_thr)} thresholds and {len(streams)} streams for {K} tasks"
+    assert lam is None or len(lam) == K, f"merge_apply_drop: {len(lam)} coefficients for {K} tasks"
+    assert rescale is None or len(rescale) == K, f"merge_apply_drop: {len(rescale)} rescale factors for {K} tasks"
+    ptrs = (C.c_void_p * max(K, 1))(*[t.data_ptr() for t in tasks])
+    lams = None if lam is None else (C.c_float * max(K, 1))(*[float(v) for v in lam])
+    thrs = (C.c_uint64 * max(K, 1))(*[int(v) for v in drop_thr])
+    resc = None if rescale is None else (C.c_float * max(K, 1))(*[float(v) for v in rescale])
+    strs = (C.c_uint32 * max(K, 1))(*[int(v) for v in streams])
+    flags = (MERGE_DROP_FLAGS["copy"] if copy else 0) | (MERGE_DROP_FLAGS["rescale"] if rescale is not None else 0)
+    if weights:
+        WEIGHTS_EPOCH += 1
+    name = "merge_mix_kernel" if copy else "merge_apply_drop_kernel"
+    _timed(f"merge_apply_drop ({name})", 4.0 * (K + 2) * n, "hbm", lambda: L.check(                      # base and K tasks read; out written
+        _lib().vd_merge_apply_drop(_p(out), _p(base), ptrs, lams, None if thr is None else _p(thr), thrs, resc, strs, K, n, MERGE_MODES[mode],
+                                   float(lam_out), int(seed), flags, _p(partial), _p(stats), _s()), "vd_merge_apply_drop"))
+    return out
+
+
 CHANNEL_ACTS = {"raw": 0, "silu_gn": 1}
 CHANNEL_JOB_INTS = 11     # x, mean, rstd, gamma, beta, B, C, HW, G, first channel, first workgroup
 
